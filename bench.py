@@ -8,8 +8,19 @@ A "step" is one pass of the hot path over one synthetic batch already resident i
 cat(lst_up, ndvi) -> ModelB_2 forward -> SIF loss (SR2) -> backward -> [gradient all-reduce] -> Adam
 (train_model_B_gradFTM.py:94-121), through the HIP path only.  Rank 0 prints ONE JSON line.
 
-`value` = patches of all ranks / wall time of the K timed steps (barrier + synchronize on both sides, max over ranks).
-Next to it, from one HIP event per step boundary on the step's stream: `ms_per_step_median` and `ms_per_step_mean_events`.
+`value` = patches of all ranks / wall time of the K timed steps (barrier + synchronize on both sides, max over ranks), and
+`ms_per_step` = that wall time / K.  Next to them, from one HIP event per step boundary on the step's stream:
+`ms_per_step_median` and `ms_per_step_mean_events`.
+
+A plain run (no --full) does only what that line needs: set up, W warm-up steps, the K timed steps, the optional output
+dump, the line.  Everything else the benchmark measures (the `roofline`, `also` and `cpu_baseline` objects below) runs
+with --full only.
+
+--dump-outputs DIR : after the timed steps, writes what the last timed step handed its caller as DIR/<name>.npy (float32):
+               train -- `ds_loss`, `percep_loss`, `loss`, the updated flat parameters `params` and the BatchNorm running
+               statistics `bn_running` (every running_mean, then running_var, in module order); infer -- `sr_tiles`, the
+               de-normalised prediction of at most 32 tiles (a fixed, seeded sample when the batch is larger).  Rank 0 only.
+               Same arguments -> same inputs (seeded model and batch), so two builds can be compared output for output.
 
 N > 1 without a launcher (`python bench.py --gpus N`, WORLD_SIZE unset): the process starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py ...`
@@ -17,7 +28,7 @@ as a CHILD before importing torch or touching HIP, relays its output and exits w
 process that has initialised the GPU).  The N > 1 line adds `allreduce_ms` (HIP events around the gradient exchange),
 `dist_backend` / `rccl_ranks`, and the per-rank wall time per step (`rank_ms_per_step_min` / `_max`).
 
-Extra objects in that line:
+Extra objects in that line with --full:
   roofline     -- the dominant kernel CLASS of the step: per-class sums of TotalDurationNs over the newest two-stream
                   profiles/*_kernel_stats.csv, the class's launches (engine layer table below) ALL timed with HIP events on
                   their launch stream INSIDE the timed steps (sifsr_profile_*): class algorithmic FLOPs per step / class
@@ -29,9 +40,9 @@ Extra objects in that line:
                   All three conv passes run in the Winograd domain (4/9 of the algorithmic multiply-adds are executed on the
                   matrix cores), so `frac` is a time-to-solution ratio against the fp32 MFMA roofline of the direct
                   algorithm, not a pipe-utilisation figure (that one is in profiles/*_mfma_util.txt).
-  also         -- measured in the same process after the timed region (N = 1, default mode): BASELINE.json config 4
-                  (`infer_b256`: eval forward of 256 tiles, hipGraph replay) and config 5 (`bf16`), so that a driver record of
-                  the default command carries them.  --no-also skips it (profiling runs).
+  also         -- measured in the same process after the timed region (N = 1, train mode): BASELINE.json config 4
+                  (`infer_b256`: eval forward of 256 tiles, hipGraph replay) and config 5 (`bf16`), so that a record of
+                  the --full command carries them.  --no-also skips it.
   cpu_baseline -- the oracle (CPU restatement of the reference, kind "port") timed on this box's host cores on a bounded
                   sample: batch 8 and batch 16, at all physical cores and at 8 threads (rank 0, N=1 only).
 
@@ -126,10 +137,11 @@ SIDE_BY_SIDE = {"fwd_16x16_256": (1, 1), "bwd16_16x16_256": (1, 2), "fwd_32x16_2
 
 def dominant_class(stats_file=None):
     """The kernel CLASS with the largest summed duration in the newest committed two-stream rocprofv3 kernel-stats file
-    (every CSV row whose name carries the class prefix is added up).  Returns (class pattern, source file)."""
+    (every CSV row whose name carries the class prefix is added up).  Returns (class pattern, source file).
+    "Newest" = last by file name: the round tags (r01a ... r03z) sort in time, file times of a checkout do not."""
     files = [stats_file] if stats_file else sorted(
         (f for f in glob.glob(os.path.join(ROOT, "profiles", "*_kernel_stats.csv"))
-         if "single" not in os.path.basename(f) and "bf16" not in os.path.basename(f)), key=os.path.getmtime)
+         if "single" not in os.path.basename(f) and "bf16" not in os.path.basename(f)), key=os.path.basename)
     table = class_table()
     for f in reversed(files):
         try:
@@ -151,7 +163,7 @@ def dominant_class(stats_file=None):
 def measured_traffic(key):
     """HBM bytes per launch of `key` from the newest committed PMC summary (profiles/*_traffic.json, written by
     tools/summarize_profile.py from separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command)."""
-    files = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_traffic.json")), key=os.path.getmtime)
+    files = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_traffic.json")), key=os.path.basename)    # newest round last
     for f in reversed(files):
         try:
             per = json.load(open(f))["per_launch"]
@@ -222,12 +234,12 @@ def parse_args(argv=None):
     ap.add_argument("--kind", default="sr2", choices=["sr2", "sr1"])
     ap.add_argument("--mode", default="train", choices=["train", "infer"])
     ap.add_argument("--roofline-class", default="auto",
-                    help="kernel class (name prefix as in kernel_class()) the roofline object reports; auto = the class with the "
+                    help="--full: kernel class (name prefix as in kernel_class()) the roofline object reports; auto = the class with the "
                          "largest time share in the newest profiles/*_kernel_stats.csv")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-solo", action="store_true", help="skip the extra single-stream steps that time the selected kernels alone "
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-solo", action="store_true", help="--full: skip the extra single-stream steps that time the selected kernels alone "
                                                             "(profiling runs: keeps the kernel trace to the steps of the benchmark itself)")
-    ap.add_argument("--no-also", action="store_true", help="skip the config-4 / config-5 measurements appended to the default line")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the config-4 / config-5 measurements appended to the line")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"],
                     help="f32 = the headline fp32 path; bf16 = BASELINE.json config 5 (bf16 MFMA operands in the 3x3 conv "
                          "forward / input-gradient / weight-gradient passes, fp32 accumulation) -- not the default")
@@ -237,7 +249,46 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run-launch", action="store_true",
                     help="N > 1 plumbing check without a GPU: every rank joins the process group (gloo), all-reduces its rank and "
                          "rank 0 prints {\"dry_run\": true, \"world\": N, \"rank_sum\": ...}")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline object (kernels timed inside the "
+                         "timed steps, then a few single-stream steps), the `also` configs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (float32, rank 0)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_MAX_TILES = 32           # --dump-outputs, --mode infer: at most 32 of the batch's 256x256 predictions (8 MB)
+
+
+def step_outputs(infer, out, model):
+    """{name: float32 numpy array} of what the last timed step handed its caller (see --dump-outputs).  Called right after
+    the timed region, before anything else runs on the model."""
+    if infer:
+        sr = out[0]
+        n = sr.shape[0]
+        if n > DUMP_MAX_TILES:
+            idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_MAX_TILES].sort().values
+            sr = sr[idx.to(sr.device)]
+        return {"sr_tiles": sr.detach().float().cpu().numpy()}
+    ds, pl, loss = out
+    named = dict(model.named_buffers())
+    running = [named[n] for n in named if n.endswith("running_mean")] + [named[n] for n in named if n.endswith("running_var")]
+    res = {"ds_loss": ds, "percep_loss": pl, "loss": loss, "params": model.flat_parameters(),
+           "bn_running": torch.cat([b.detach().reshape(-1) for b in running])}
+    return {k: v.detach().float().reshape(-1).cpu().numpy() for k, v in res.items()}
+
+
+def dump_outputs(arrays, out_dir):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 * 10**6, f"--dump-outputs: {total} bytes > 64 MB"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    print(f"[bench] wrote {len(arrays)} arrays ({total / 1e6:.2f} MB) to {out_dir}", file=sys.stderr, flush=True)
 
 
 def self_launch(args):
@@ -371,17 +422,18 @@ def main():
     for _ in range(args.warmup):
         step()
 
-    # ---- kernels timed inside the timed steps (event pools are created here, outside the timed region): every launch of the
-    # dominant class + the three passes of inbloc.bloc.3 side by side
-    table = class_table()
-    dom_cls, dom_src = (args.roofline_class, "--roofline-class") if args.roofline_class != "auto" else dominant_class()
-    if dom_cls not in table:
-        raise SystemExit(f"--roofline-class {dom_cls!r}: not one of {sorted(table)}")
+    # ---- --full: kernels timed inside the timed steps (event pools are created here, outside the timed region): every launch
+    # of the dominant class + the three passes of inbloc.bloc.3 side by side
     selections = []                                   # [(layer, phase)] in slot order; on EVERY rank: the extra single-stream
-    if not infer:                                     # steps below contain the gradient all-reduce, a collective
-        for lp in (list(table[dom_cls]) if args.dtype == "f32" else []) + list(SIDE_BY_SIDE.values()):
-            if lp not in selections:
-                selections.append(lp)
+    if args.full:                                     # steps below contain the gradient all-reduce, a collective
+        table = class_table()
+        dom_cls, dom_src = (args.roofline_class, "--roofline-class") if args.roofline_class != "auto" else dominant_class()
+        if dom_cls not in table:
+            raise SystemExit(f"--roofline-class {dom_cls!r}: not one of {sorted(table)}")
+        if not infer:
+            for lp in (list(table[dom_cls]) if args.dtype == "f32" else []) + list(SIDE_BY_SIDE.values()):
+                if lp not in selections:
+                    selections.append(lp)
 
     def select_all():
         for j, (layer, phase) in enumerate(selections):
@@ -414,8 +466,11 @@ def main():
     dt_local = dt = time.perf_counter() - t0
     dp.set_allreduce_timer(None)
     per_step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step_outputs(infer, out, model), args.dump_outputs)
     ktimes = read_all()
-    L.call("sifsr_profile_select", -1, 0)
+    if selections:
+        L.call("sifsr_profile_select", -1, 0)
     # The weight-gradient kernels run on the library's second stream BESIDE the rest of the backward pass, so their in-step
     # duration is that of a kernel sharing the machine.  A few extra, untimed steps with the single-stream schedule give the
     # same launches' stand-alone durations, reported next to the in-step ones (`solo_ms`).
@@ -481,11 +536,11 @@ def main():
         step_obj = {"achieved": round(step_tf, 2), "frac": round(step_tf / PEAK_FP32_MFMA_TFLOPS, 4),
                     "hbm_GBs_algorithmic": round(bytes_unit * per_gpu / 1e9, 1),
                     "ceiling_units_per_s": round(PEAK_FP32_MFMA_TFLOPS * 1e12 / flops_unit, 0)}
-        if infer:
+        if args.full and infer:
             out_json["roofline"] = {"bound": "mfma", "kernel": "whole eval forward (graph replay)", "achieved": round(step_tf, 2),
                                     "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": round(step_tf / PEAK_FP32_MFMA_TFLOPS, 4),
                                     "traffic": None, "step": step_obj}
-        elif args.dtype == "f32":
+        elif args.full and args.dtype == "f32":
             def entry(lp):
                 avg_ms, n = ktimes[lp]
                 fl = member_flops(*lp) * batch
@@ -520,7 +575,7 @@ def main():
                 "traffic": traffic, "traffic_unit": "HBM bytes per launch, class average (PMC)", "traffic_source": traffic_src,
                 "members": members, "kernels": side, "step": step_obj,
             }
-        else:
+        elif args.full:
             # bf16 operands: the matrix-core peak rises 16x, the bytes do not change (fp32 storage) -> HBM-bound
             # (SURVEY.md §8 d).  Algorithmic bytes of inbloc.bloc.3's forward launch = its input + output activations.
             avg_ms, n = ktimes[(1, 1)]
@@ -540,9 +595,9 @@ def main():
                                    "what": "inputs start in pinned host memory every step (double-buffered async H2D on a second stream)"
                                            + ("; output copied back to pinned host memory" if infer else "")
                                            + " -- the PCIe-inclusive rate, not the headline value"}
-        if world == 1 and not infer and args.dtype == "f32" and not args.no_also:
+        if args.full and world == 1 and not infer and args.dtype == "f32" and not args.no_also:
             out_json["also"] = also_configs(sifsr, dev, stats, lst, lst_up, ndvi, alpha, gamma, lr, kind)
-        if world == 1 and not args.no_cpu_baseline and not infer:
+        if args.full and world == 1 and not args.no_cpu_baseline and not infer:
             out_json["cpu_baseline"] = cpu_baseline(kind, alpha, gamma, lr, stats["mean_lst"], stats["std_lst"])
         print(json.dumps(out_json), flush=True)
     if world > 1:

@@ -124,29 +124,16 @@ def test_tile_granule(sifsr):
 
 def test_dropin_modules_cover_the_reference_scripts_names():
     """dropin/{model,dataset,utils}.py must offer every name the reference's three training scripts and predict.py take
-    from ``model`` / ``dataset`` / ``utils`` (SURVEY.md §8 b).  The names are read from the reference's scripts when
-    they are present (build container); the committed list below is what that reading gave, so the check also runs
-    where /root/reference does not exist."""
+    from ``model`` / ``dataset`` / ``utils`` (SURVEY.md §8 b).  The list below is what an ``ast`` reading of those four
+    scripts gives (``from model/dataset import ...`` and every ``us.<name>`` attribute), less the GDAL HDF readers of
+    predict.py (``read_LST``, ``read_NIRRED``, ``compute_NDVI``: out of scope); it is committed, so the check needs
+    nothing outside the repository."""
     import ast
-    import importlib.util
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     need = {"model": {"ModelB_2"}, "dataset": {"ModisDatasetB", "ModisDatasetB_scale_invariance"},
             "utils": {"downscale_LST_SR_to_LR", "get_output_ftm", "model_checkpoint", "psnr_skimage", "ssim_skimage",
                       "read_JsonB", "save_model", "upsampling"}}
-    ref = "/root/reference"
-    io_only = {"read_LST", "read_NIRRED", "compute_NDVI"}          # GDAL HDF readers of predict.py: out of scope
-    if os.path.isdir(ref):
-        found = {"model": set(), "dataset": set(), "utils": set()}
-        for f in ("train_model_B_gradFTM.py", "train_model_B_predef_filters.py", "train_model_B_scale_invariance.py", "predict.py"):
-            tree = ast.parse(open(os.path.join(ref, f)).read())
-            for node in ast.walk(tree):
-                if isinstance(node, ast.ImportFrom) and node.module in ("model", "dataset"):
-                    found[node.module].update(a.name for a in node.names)
-                if isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id == "us":
-                    found["utils"].add(node.attr)
-        found["utils"] -= io_only
-        assert found == need, found
     src = {m: open(os.path.join(root, "dropin", m + ".py")).read() for m in need}
     for mod, names in need.items():
         tree = ast.parse(src[mod])
@@ -271,3 +258,34 @@ def test_bench_roofline_class_selection(tmp_path):
                  '"bn_finalize_kernel",100,9999\n')
     cls, src = bench.dominant_class(str(f))
     assert cls == "conv3x3_wino8_kernel<4, true" and src == "x_kernel_stats.csv"      # 300 + 250 > 500 + 40
+
+
+def test_bench_options():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times exactly K steps and leaves everything beyond the headline line to
+    --full (off by default); --dump-outputs takes a directory; a run without timed steps is refused."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.gpus, a.steps, a.warmup, a.full, a.dump_outputs) == (1, 7, 2, False, None)
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_bench_roofline_sources_follow_the_round_tag(tmp_path, monkeypatch):
+    """Without an explicit file, bench.py --full reads the newest round's profiles, by name: a fresh checkout gives every
+    committed file the same (or an arbitrary) modification time."""
+    import bench
+    prof = tmp_path / "profiles"
+    prof.mkdir()
+    row = '"Name","Calls","TotalDurationNs"\n"void conv3x3_%s(ConvArgs)",1,100\n'
+    (prof / "r03z_kernel_stats.csv").write_text(row % "bwd16_kernel<true>")
+    (prof / "r01a_kernel_stats.csv").write_text(row % "wino8_kernel<4, true, true, 1>")
+    (prof / "r03z_traffic.json").write_text('{"per_launch": {"conv3x3_bwd16_kernel": {"bytes": 3}}}')
+    (prof / "r01a_traffic.json").write_text('{"per_launch": {"conv3x3_bwd16_kernel": {"bytes": 1}}}')
+    os.utime(prof / "r03z_kernel_stats.csv", (1, 1))
+    os.utime(prof / "r03z_traffic.json", (1, 1))
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    assert bench.dominant_class() == ("conv3x3_bwd16_kernel", "r03z_kernel_stats.csv")
+    assert bench.measured_traffic("conv3x3_bwd16_kernel") == (3, "r03z_traffic.json")
