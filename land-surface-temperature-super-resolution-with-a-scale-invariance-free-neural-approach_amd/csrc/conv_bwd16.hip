@@ -540,7 +540,8 @@ bool conv3x3_bwd16_applies(int B, int H, int W) {
 
 int conv3x3_bwd16_grid(int B, int H, int W) {
   const int ntiles = B * (H / 16) * (W / 16);
-  static const int dbg = getenv("SIFSR_DBG_BWD16_GRID") ? atoi(getenv("SIFSR_DBG_BWD16_GRID")) : 256;   // one workgroup per CU
+  static const int dbg_env = getenv("SIFSR_DBG_BWD16_GRID") ? atoi(getenv("SIFSR_DBG_BWD16_GRID")) : 256;   // one workgroup per CU
+  static const int dbg = dbg_env >= 1 ? dbg_env : 256;   // 0 / negative / unparsable: the default (the walk divides by it)
   if (ntiles <= dbg) return ntiles;
   const int rounds = (ntiles + dbg - 1) / dbg;
   int g = (ntiles + rounds - 1) / rounds;

@@ -666,7 +666,7 @@ int sifsr_engine_backward(const float* x, const float* dsr, const float* params,
   // the upsample adjoint that completes g of a low-resolution layer also leaves that layer's BatchNorm-backward sums (one
   // row per workgroup): up_rows > 0 tells the next bn_unit_bwd of that layer to skip its reduce pass
   int up_rows = 0;
-  int last_fused = -1;   // the last layer whose slabs the fused 16 -> 16 kernel wrote on the caller's stream (its ev[] marks them complete)
+  int last_fused = -1;   // the last layer (decoder, encoder or inbloc) whose slabs the fused 16 -> 16 kernel wrote on the caller's stream (its ev[] marks them complete)
   for (int k = 2; k >= 0; --k) {
     const int lv = 2 - k;
     const int la = dec_a[k], lb = dec_b[k], ls = dec_skip[k], ll = dec_low[k];
@@ -722,6 +722,7 @@ int sifsr_engine_backward(const float* x, const float* dsr, const float* params,
     SIFSR_TRY(bn_unit_bwd(c, lb, c.f(w.g[lb]), grads, nullptr, rows_b));
     bool fused_b = false;
     SIFSR_TRY(conv_unit_bwd16(c, lb, src_act(c, la), c.f(w.g[lb]), c.f(w.g[la]), nullptr, la, &rows_a, 1, &fused_b));
+    if (fused_b) last_fused = lb;
     if (!fused_b) {
       SIFSR_TRY(conv_unit_wgrad(c, lb, src_act(c, la), src_none(), c.f(w.g[lb]), grads));
       SIFSR_TRY(conv_unit_dgrad(c, lb, c.f(w.g[lb]), c.f(w.g[la]), pc[k], pc[k], nullptr, 0, nullptr, la, &rows_a));
@@ -729,6 +730,7 @@ int sifsr_engine_backward(const float* x, const float* dsr, const float* params,
     SIFSR_TRY(bn_unit_bwd(c, la, c.f(w.g[la]), grads, nullptr, rows_a));
     bool fused_a = false;
     SIFSR_TRY(conv_unit_bwd16(c, la, src_raw(c.f(w.P[k]), pc[k]), c.f(w.g[la]), c.f(w.gP[k]), c.f(w.g[lb]), -1, nullptr, 1, &fused_a));
+    if (fused_a) last_fused = la;
     if (!fused_a) {
       SIFSR_TRY(conv_unit_wgrad(c, la, src_raw(c.f(w.P[k]), pc[k]), src_none(), c.f(w.g[la]), grads));
       SIFSR_TRY(conv_unit_dgrad(c, la, c.f(w.g[la]), c.f(w.gP[k]), pc[k], pc[k], nullptr, 0, c.f(w.g[lb])));
@@ -749,14 +751,16 @@ int sifsr_engine_backward(const float* x, const float* dsr, const float* params,
                             pool_on_load ? c.f(w.gP[0]) : nullptr));
   if (pool_on_load && !fused_in3) return SIFSR_ERR_ARG;
   if (head_linear && !fused_in3) return SIFSR_ERR_ARG;
+  if (fused_in3) last_fused = L_IN3;
   if (!fused_in3) SIFSR_TRY(conv_unit_wgrad(c, L_IN3, src_act(c, L_IN0), src_none(), c.f(w.g[L_IN3]), grads));
   // that was the last MFMA layer: all 16 layers' weight-gradient slabs -> OIHW gradients, one launch.  With the second
   // stream it follows the last weight gradient there (it writes only the conv-weight regions of `grads`, which nothing
   // on the caller's stream touches) and overlaps the head of the chain instead of trailing it.  The fused 16 -> 16 kernels
-  // wrote their slabs on the CALLER's stream: the last of them (this layer's) is what the second stream waits for.
+  // wrote their slabs on the CALLER's stream: the last of them (ev[] recorded in enqueue order, so it covers every earlier
+  // one) is what the second stream waits for.
   if (c.side != nullptr) {
-    if (fused_in3) {
-      if (hipStreamWaitEvent(c.side->s, c.side->ev[L_IN3], 0) != hipSuccess) return SIFSR_ERR_ARG;
+    if (last_fused >= 0) {
+      if (hipStreamWaitEvent(c.side->s, c.side->ev[last_fused], 0) != hipSuccess) return SIFSR_ERR_ARG;
       lane_guard.forked = true;
     }
     SIFSR_TRY(finish_wgrads(c.side->s));

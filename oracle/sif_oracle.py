@@ -378,22 +378,31 @@ LOSSES = {"sr2": sr2_loss, "sr1": sr1_loss, "si": si_loss}
 # ----------------------------------------------------------------------------------------------
 # Train step (train_model_B_gradFTM.py:86-121 / train_model_B_predef_filters.py:98-137)
 # ----------------------------------------------------------------------------------------------
-def forward_backward(sd, lst, lst_up, ndvi, mean, std, alpha, gamma, kind="sr2"):
-    """One fwd + loss + backward in training mode.  Returns (sr, (ds, pl, loss), grads dict).
-
-    ``sd`` BN buffers are updated exactly as ``model.train(); model(x)`` would.
-    """
+def forward_with_leaves(sd, lst_up, ndvi):
+    """The training-mode forward of ``forward_backward`` with its graph kept: returns (sr, leaves), ``leaves`` the parameters as
+    autograd leaves in ``param_names()`` order.  ``torch.autograd.grad(sr, leaves, dsr)`` is then the parameter gradient for
+    any upstream gradient ``dsr`` (at fixed ReLU masks the backward is linear in it).  ``sd`` BN buffers are updated exactly as
+    ``model.train(); model(x)`` would."""
     names = param_names()
     leaves = {n: sd[n].detach().clone().requires_grad_(True) for n in names}
     work = OrderedDict((k, leaves.get(k, v)) for k, v in sd.items())
     x = torch.cat((lst_up, ndvi), dim=1)                       # :94
     sr = modelb2_forward(work, x, training=True)               # :96
-    ds, pl, loss = LOSSES[kind](sr, lst, ndvi, mean, std, alpha, gamma)
-    grads = torch.autograd.grad(loss, [leaves[n] for n in names])
     for k in sd:                                               # carry BN buffer updates back
         if k.endswith(("running_mean", "running_var", "num_batches_tracked")):
             sd[k] = work[k].detach()
-    return sr.detach(), (ds.detach(), pl.detach(), loss.detach()), dict(zip(names, grads))
+    return sr, [leaves[n] for n in names]
+
+
+def forward_backward(sd, lst, lst_up, ndvi, mean, std, alpha, gamma, kind="sr2"):
+    """One fwd + loss + backward in training mode.  Returns (sr, (ds, pl, loss), grads dict).
+
+    ``sd`` BN buffers are updated exactly as ``model.train(); model(x)`` would.
+    """
+    sr, leaves = forward_with_leaves(sd, lst_up, ndvi)
+    ds, pl, loss = LOSSES[kind](sr, lst, ndvi, mean, std, alpha, gamma)
+    grads = torch.autograd.grad(loss, leaves)
+    return sr.detach(), (ds.detach(), pl.detach(), loss.detach()), dict(zip(param_names(), grads))
 
 
 class AdamState:

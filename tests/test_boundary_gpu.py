@@ -165,6 +165,7 @@ def test_predict_py_call_pattern_with_cpu_tensors(sifsr, golden, dropin):
         assert isinstance(lst_sr, np.ndarray) and lst_sr.shape == (256, 256)
         outs.append(torch.from_numpy(lst_sr))
     check_digest(torch.stack(outs)[:, None], c["y_denorm"], TOL)
+    check_digest((torch.stack(outs)[:, None].double() - MEAN) / STD, c["y"], TOL)      # the same bar on the network's own scale
     # model_perf_aster_formatds.py:189-203
     x_lst_ndvi = torch.cat((lst_up[0:1], ndvi[0:1]), dim=1)
     with torch.inference_mode():

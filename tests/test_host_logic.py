@@ -289,3 +289,33 @@ def test_bench_roofline_sources_follow_the_round_tag(tmp_path, monkeypatch):
     monkeypatch.setattr(bench, "ROOT", str(tmp_path))
     assert bench.dominant_class() == ("conv3x3_bwd16_kernel", "r03z_kernel_stats.csv")
     assert bench.measured_traffic("conv3x3_bwd16_kernel") == (3, "r03z_traffic.json")
+
+
+GRID_WORKER = r'''
+import os, sys
+sys.path.insert(0, os.environ["SIFSR_ROOT"])
+from sifsr import _lib
+print(_lib.call("sifsr_model_workspace_bytes", 64, 256, 256, 1))
+'''
+
+
+def test_bwd16_grid_knob_below_one_falls_back_to_the_default():
+    """SIFSR_DBG_BWD16_GRID sizes the fused 16 -> 16 backward's persistent grid, and the workspace layout asks for that grid
+    (conv3x3_bwd16_grid divides by the knob).  0 used to kill the process with SIGFPE and a negative value gave a launch of grid 0:
+    values below 1 fall back to the default, so the workspace of the bench shape must be the one without the knob.  The knob is
+    read once per process, so each value runs in a child of its own."""
+    import subprocess
+
+    def workspace_bytes(knob):
+        env = {k: v for k, v in os.environ.items() if k != "SIFSR_DBG_BWD16_GRID"}
+        env["SIFSR_ROOT"] = ROOT
+        if knob is not None:
+            env["SIFSR_DBG_BWD16_GRID"] = knob
+        r = subprocess.run([sys.executable, "-c", GRID_WORKER], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (knob, r.returncode, r.stdout[-2000:] + r.stderr[-3000:])
+        return int(r.stdout.strip().splitlines()[-1])
+
+    ref = workspace_bytes(None)
+    assert ref > 0
+    for knob in ("0", "-5"):
+        assert workspace_bytes(knob) == ref, knob

@@ -58,15 +58,56 @@ def test_eval_forward_vs_oracle_and_golden(sifsr, golden):
         check_digest(y.cpu(), c["y"], TOL)
         out = sifsr.predict.predict_tiles(m, lst_up.cuda(), ndvi.cuda(), {"mean_lst": MEAN, "std_lst": STD}, batch=1)
         check_digest(out.cpu(), c["y_denorm"], TOL)
+        check_digest((out.cpu().double() - MEAN) / STD, c["y"], TOL)      # the same bar on the network's own scale
         # eval mode must not touch the BN buffers
         for k, v in m.state_dict().items():
             assert torch.equal(v.cpu(), sd[k]), k
 
 
+def read_masks(ws, B, H, W):
+    """The ReLU masks a HIP training forward took, read back from its workspace: {bn prefix: bool (B,C,h,w)} on the host."""
+    import ctypes
+    from sifsr import _lib as L
+    reg = (ctypes.c_size_t * 56)()
+    assert L.call("sifsr_model_workspace_regions", B, H, W, reg, 56) == 56
+    tab = (ctypes.c_int * (17 * 8))()
+    assert L.call("sifsr_layer_table", tab, 17) == 17
+    masks = {}
+    for l, (conv, bn, cin, cout) in enumerate(O.CONV_BN_LAYERS):
+        lv, choff = tab[l * 8 + 2], tab[l * 8 + 7]
+        h, w = H >> lv, W >> lv
+        y = ws[reg[l]:reg[l] + B * h * w * cout].view(B, h, w, cout)
+        sc = ws[reg[54] + choff:reg[54] + choff + cout]
+        sh = ws[reg[55] + choff:reg[55] + choff + cout]
+        # sign of the kernels' fmaf(y, scale, shift): evaluate y*scale+shift in float64 (exact product)
+        masks[bn] = ((y.double() * sc.double() + sh.double()) > 0).permute(0, 3, 1, 2).cpu()
+    return masks
+
+
+def normalised_per_image_err(out, y_ref, mean=MEAN, std=STD):
+    """A de-normalised prediction (y * std + mean, ~307 K) taken back to the network's own scale in float64 and compared with
+    the network output ``y_ref`` per image: max|(out - mean) / std - y_ref| / max|y_ref| for each image (N,).  Comparing
+    the de-normalised values with a relative bar divides by ~300 K instead of by max|y| ~ 8: 7-9x looser than it reads."""
+    return per_image_rel_err((out.detach().double().cpu() - mean) / std, y_ref)
+
+
+def per_image_rel_err(a, ref):
+    """max|a - ref| / max|ref| per image (leading dimension), in float64."""
+    a, r = a.detach().double().cpu(), ref.detach().double().cpu()
+    dims = tuple(range(1, r.dim()))
+    return (a - r).abs().amax(dim=dims) / r.abs().amax(dim=dims).clamp_min(1e-30)
+
+
+def oracle_eval_y(sd, lst_up, ndvi, dtype=torch.float64):
+    """The oracle's eval-mode network output y (normalised domain) in ``dtype``."""
+    sdd = {k: (v.to(dtype) if v.is_floating_point() else v.clone()) for k, v in sd.items()}
+    with torch.inference_mode():
+        return O.modelb2_forward(sdd, torch.cat((lst_up, ndvi), 1).to(dtype), training=False)
+
+
 def _hip_forward_backward(sifsr, sd, lst, lst_up, ndvi, alpha, gamma, kind):
     """fwd + loss + bwd through the C ABI, keeping the workspace so the test can read the ReLU masks
     (sign of y*scale+shift per layer) the HIP forward took.  Returns (sr, losses, grads{name}, masks{bn})."""
-    import ctypes
     from sifsr import _lib as L
     m = make_model(sifsr, sd).train()
     x = torch.cat((lst_up, ndvi), 1).cuda()
@@ -87,19 +128,7 @@ def _hip_forward_backward(sifsr, sd, lst, lst_up, ndvi, alpha, gamma, kind):
     grads = torch.empty_like(fp)
     L.call("sifsr_model_backward", x, dsr.contiguous(), fp, grads, ws, wsb, B, H, W, S)
     torch.cuda.synchronize()
-    reg = (ctypes.c_size_t * 56)()
-    assert L.call("sifsr_model_workspace_regions", B, H, W, reg, 56) == 56
-    tab = (ctypes.c_int * (17 * 8))()
-    assert L.call("sifsr_layer_table", tab, 17) == 17
-    masks = {}
-    for l, (conv, bn, cin, cout) in enumerate(O.CONV_BN_LAYERS):
-        lv, choff = tab[l * 8 + 2], tab[l * 8 + 7]
-        h, w = H >> lv, W >> lv
-        y = ws[reg[l]:reg[l] + B * h * w * cout].view(B, h, w, cout)
-        sc = ws[reg[54] + choff:reg[54] + choff + cout]
-        sh = ws[reg[55] + choff:reg[55] + choff + cout]
-        # sign of the kernels' fmaf(y, scale, shift): evaluate y*scale+shift in float64 (exact product)
-        masks[bn] = ((y.double() * sc.double() + sh.double()) > 0).permute(0, 3, 1, 2).cpu()
+    masks = read_masks(ws, B, H, W)
     g, off = {}, 0
     for n, p in m.named_parameters():
         g[n] = grads[off:off + p.numel()].view(p.shape).cpu()
@@ -333,11 +362,14 @@ def test_graph_captured_inference(sifsr, golden):
         out = gp(lst_up.cuda(), ndvi.cuda())
         assert torch.equal(out, eager)
     check_digest(out.cpu(), c["y_denorm"], TOL)
+    check_digest((out.cpu().double() - MEAN) / STD, c["y"], TOL)
     # a different input through the same captured graph
     lst2, lst_up2, ndvi2 = O.synthetic_batch(99, 3)
     out2 = gp(lst_up2.cuda(), ndvi2.cuda())
     ref2 = O.predict_tiles(sd, lst_up2, ndvi2, MEAN, STD)
     assert rel_err(out2, ref2) < TOL
+    err = normalised_per_image_err(out2, oracle_eval_y(sd, lst_up2, ndvi2))
+    assert float(err.max()) < TOL, err
 
 
 @pytest.mark.parametrize("shape", [(2, 128, 384), (3, 64, 64), (2, 48, 80), (1, 32, 32), (2, 40, 72), (1, 24, 24)])
@@ -532,7 +564,6 @@ def test_bench_workload_forward_and_loss_vs_oracle(sifsr):
 def _hip_step_reading_masks(sifsr, m, opt, lst, lst_up, ndvi, alpha, gamma, kind):
     """One optimisation step through the C ABI with the workspace kept, so that the ReLU masks the HIP forward took can be
     read back (as _hip_forward_backward), followed by the FlatAdam kernel.  Returns (losses, masks)."""
-    import ctypes
     from sifsr import _lib as L
     m.train()
     x = torch.cat((lst_up, ndvi), 1)
@@ -549,18 +580,7 @@ def _hip_step_reading_masks(sifsr, m, opt, lst, lst_up, ndvi, alpha, gamma, kind
     grads = torch.empty_like(fp)
     L.call("sifsr_model_backward", x, dsr.contiguous(), fp, grads, ws, wsb, B, H, W, S)
     torch.cuda.synchronize()
-    reg = (ctypes.c_size_t * 56)()
-    assert L.call("sifsr_model_workspace_regions", B, H, W, reg, 56) == 56
-    tab = (ctypes.c_int * (17 * 8))()
-    assert L.call("sifsr_layer_table", tab, 17) == 17
-    masks = {}
-    for l, (conv, bn, cin, cout) in enumerate(O.CONV_BN_LAYERS):
-        lv, choff = tab[l * 8 + 2], tab[l * 8 + 7]
-        h, w = H >> lv, W >> lv
-        y = ws[reg[l]:reg[l] + B * h * w * cout].view(B, h, w, cout)
-        sc = ws[reg[54] + choff:reg[54] + choff + cout]
-        sh = ws[reg[55] + choff:reg[55] + choff + cout]
-        masks[bn] = ((y.double() * sc.double() + sh.double()) > 0).permute(0, 3, 1, 2).cpu()
+    masks = read_masks(ws, B, H, W)
     off = 0
     for p in m.parameters():
         p.grad = grads[off:off + p.numel()].view(p.shape)
@@ -630,6 +650,7 @@ def test_statistics_matched_state_eval_and_train(sifsr, kind):
     check_digest(y.cpu(), c["y_eval"], TOL)
     out = sifsr.predict.predict_tiles(m, lst_up.cuda(), ndvi.cuda(), {"mean_lst": MEAN, "std_lst": STD}, batch=1)
     check_digest(out.cpu(), c["y_denorm"], TOL)
+    check_digest((out.cpu().double() - MEAN) / STD, c["y_eval"], TOL)
 
     sr, (ds, pl, loss), grads, masks, mt = _hip_forward_backward(sifsr, sd, lst, lst_up, ndvi, c["alpha"], c["gamma"], kind)
     check_digest(sr, c["sr"], TOL)

@@ -10,6 +10,7 @@ import torch
 
 from oracle import sif_oracle as O
 from tests.conftest import rel_err
+from tests.test_model_gpu import normalised_per_image_err
 
 pytestmark = pytest.mark.gpu
 STATS = {"mean_lst": 307.2378, "std_lst": 5.5698, "mean_ndvi": 0.6452, "std_ndvi": 0.1683}
@@ -49,6 +50,16 @@ def test_predict_granule(sifsr):
     assert out.shape == ref.shape
     assert rel_err(out.cpu(), ref) < 1e-4
     assert out[4 * 192:, :].abs().max().item() == 0 and out[:, 4 * 128:].abs().max().item() == 0
+    # the pasted pixels on the network's own scale, per 256 x 256 tile, against the float64 oracle (a relative bar on the
+    # de-normalised ~307 K values above is 7-9x looser than it reads)
+    sd64 = {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}
+    ref64 = O.predict_granule(sd64, lst_g.double(), ndvi_g.double(), STATS)
+
+    def tiles(t):
+        return t[:4 * 192, :4 * 128].reshape(3, 256, 2, 256).permute(0, 2, 1, 3).reshape(6, 1, 256, 256)
+    y_ref = (tiles(ref64) - STATS["mean_lst"]) / STATS["std_lst"]
+    err = normalised_per_image_err(tiles(out.cpu()), y_ref, STATS["mean_lst"], STATS["std_lst"])
+    assert float(err.max()) < 1e-4, err
 
 
 @pytest.mark.parametrize("shape,kelvin", [((3, 1, 256, 256), False), ((2, 1, 96, 80), True)])
