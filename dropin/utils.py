@@ -5,6 +5,7 @@ training scripts use, the hot-path ones on MI355X:
   us.generate_psf_kernel                           utils.py:1615          -> host, float64 -> fp32 (as the reference)
   us.psnr_skimage, us.ssim_skimage                 utils.py:548-578       -> device kernel; accept the numpy arrays the
                                                                              scripts pass (.detach().cpu().numpy()) or tensors
+  us.gssim                                         utils.py:1904-2005     -> device kernel (sifsr.metrics.aster_metrics)
   us.model_checkpoint                              utils.py:667-714       -> sifsr.train.ModelCheckpoint
   us.read_JsonA/B/C, us.save_model, us.load_model  utils.py:718-826       -> plain host code
   us.upsampling                                    utils.py:163-180       -> bicubic x scale, OpenCV INTER_CUBIC semantics
@@ -52,6 +53,22 @@ def psnr_skimage(predictions, targets):
 def ssim_skimage(predictions, targets):
     """utils.py:554-578 -> float (batch mean)."""
     return float(_metrics.psnr_ssim(*_dev_pair(predictions, targets))[1])
+
+
+def gssim(im1, im2, win_size=7, data_range=None, grad_comp_type=1):
+    """utils.py:1904-2005 -> float, computed on the GPU (the GSSIM column of sifsr.metrics.aster_metrics).  im1, im2: (H,W)
+    float32 numpy arrays (or device tensors), H, W >= 16; ``grad_comp_type`` is accepted and ignored, as in the reference."""
+    if data_range is None:
+        raise TypeError("gssim: data_range=None is not supported (the reference computes K1 * None and fails)")
+    if win_size != 7:
+        raise NotImplementedError("gssim: only win_size=7 (the reference's default) has a gfx950 kernel")
+    for name, im in (("im1", im1), ("im2", im2)):
+        if isinstance(im, torch.Tensor) and not im.is_cuda:
+            raise sifsr.SifsrError(f"gssim: {name} is on {im.device}; pass a numpy array or a device tensor")
+    a, b = _dev_pair(im1, im2)
+    if a.dim() != 2 or a.shape != b.shape:
+        raise ValueError(f"gssim: two 2-D images of the same shape expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    return float(_metrics.aster_metrics(a[None, None], b[None, None], data_range=float(np.float32(data_range)))[0, 6])
 
 
 def upsampling(img, scale):

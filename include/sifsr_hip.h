@@ -308,6 +308,23 @@ SIFSR_API size_t sifsr_psnr_ssim_scratch_bytes(int B, int H, int W);
 SIFSR_API int sifsr_psnr_ssim(const float* pred, const float* targ, int B, int H, int W, void* scratch, size_t scratch_bytes,
                               float* out2, void* stream);
 
+/* Per-pair ASTER evaluation metrics: the table of model_perf_aster_formatds.py:371-437 without LPIPS, for
+ * B pairs of (B,1,H,W) images, ref = ASTER (overlap_11, im1), pred = prediction (overlap_22, im2); any H, W >= 16.
+ * out8 (device, (B,8) float64) rows follow the column names of :507 without 'LPIPS':
+ *   PSNR, SSIM (skimage 0.22 defaults, :430-431), RMSE (:432), RMSE low / mean / high grad (:379-404; g = |ref -
+ *   get_output_ftm(ref)|, q25 / q75 = np.percentile(g, 25 / 75), divisor N), GSSIM (us.gssim, utils.py:1904-2005),
+ *   RMSE_grad (:414-437, 4-kernel Sobel bank, 'valid').
+ * data_range < 0: R = max(ref u pred) - min(ref u pred) per pair in float32 (:373-374); >= 0: that R for every pair.
+ * taps9: 9 HOST floats as for sifsr_gauss9_reflect_fwd (mtf 0.1, factor 4).  scratch: device, >= the _scratch_bytes. */
+SIFSR_API size_t sifsr_eval_metrics_scratch_bytes(int B, int H, int W);
+SIFSR_API int sifsr_eval_metrics(const float* ref, const float* pred, int B, int H, int W, const float* taps9, float data_range,
+                                 void* scratch, size_t scratch_bytes, double* out8, void* stream);
+/* The gradient strata of model_perf_aster_formatds.py:379-404 alone: g (B,1,H,W) = |ref - get_output_ftm(ref)|,
+ * q2 (B,2) float32 = np.percentile(g, [25, 75]) per image (numpy 2.x 'linear', exact order statistics),
+ * counts3 (B,3) int32 = #(g < q25), #(q25 <= g <= q75), #(g >= q75). */
+SIFSR_API int sifsr_gradient_strata(const float* ref, int B, int H, int W, const float* taps9, float* g, float* q2, int* counts3,
+                                    void* stream);
+
 /* us.downsampling (utils.py:183-213), the 'norm-L4' decimation used by the scale-invariance baseline's dataset
  * (dataset.py:258): out[b][i][j] = (mean over the 4x4 block of x^4)^(1/4); x (B,H,W), H and W multiples of 4. */
 SIFSR_API int sifsr_l4pool4(const float* x, float* out, int B, int H, int W, void* stream);

@@ -541,6 +541,22 @@ int sifsr_psnr_ssim(const float* pred, const float* targ, int B, int H, int W, v
   return launch_psnr_ssim(pred, targ, B, H, W, scratch, out2, S(stream));
 }
 
+// ---- per-pair ASTER evaluation metrics ----
+size_t sifsr_eval_metrics_scratch_bytes(int B, int H, int W) { return eval_metrics_scratch_bytes(B, H, W); }
+int sifsr_eval_metrics(const float* ref, const float* pred, int B, int H, int W, const float* taps9, float data_range,
+                       void* scratch, size_t scratch_bytes, double* out8, void* stream) {
+  if (!ref || !pred || !taps9 || !scratch || !out8) return SIFSR_ERR_ARG;
+  const size_t need = eval_metrics_scratch_bytes(B, H, W);
+  if (need == 0) return SIFSR_ERR_SHAPE;
+  if (scratch_bytes < need) return SIFSR_ERR_WORKSPACE;
+  return launch_eval_metrics(ref, pred, B, H, W, taps9, data_range, scratch, out8, S(stream));
+}
+int sifsr_gradient_strata(const float* ref, int B, int H, int W, const float* taps9, float* g, float* q2, int* counts3,
+                          void* stream) {
+  if (!ref || !taps9 || !g || !q2 || !counts3) return SIFSR_ERR_ARG;
+  return launch_gradient_strata(ref, B, H, W, taps9, g, q2, counts3, S(stream));
+}
+
 // ---- Fourier-domain evaluation ----
 size_t sifsr_fft2_attenuation_scratch_bytes(int B, int H, int W) { return fourier_scratch_bytes(B, H, W); }
 int sifsr_fft2_attenuation(const float* img, int B, int H, int W, void* scratch, size_t scratch_bytes, float* mag,

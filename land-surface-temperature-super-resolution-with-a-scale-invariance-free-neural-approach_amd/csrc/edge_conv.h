@@ -85,6 +85,13 @@ int launch_l4pool4(const float* x, float* out, int B, int H, int W, hipStream_t 
 size_t psnr_ssim_scratch_bytes(int B, int H, int W);
 int launch_psnr_ssim(const float* pred, const float* targ, int B, int H, int W, void* scratch, float* out2, hipStream_t s);
 
+// ---- eval_metrics.hip ---- (per-pair ASTER evaluation metrics)
+size_t eval_metrics_scratch_bytes(int B, int H, int W);
+int launch_eval_metrics(const float* a, const float* b, int B, int H, int W, const float* taps9, float data_range,
+                        void* scratch, double* out8, hipStream_t s);
+int launch_gradient_strata(const float* a, int B, int H, int W, const float* taps9, float* g, float* q2, int* counts3,
+                           hipStream_t s);
+
 // ---- fourier.hip ---- (Fourier-domain evaluation)
 size_t fourier_scratch_bytes(int B, int H, int W);
 int launch_fft2_attenuation(const float* img, int B, int H, int W, void* scratch, float* mag, float* spectrum, hipStream_t s);

@@ -7,12 +7,16 @@ it: ``data_range = targets.max() - targets.min()`` over the WHOLE target batch, 
 ``peak_signal_noise_ratio = 10 log10(range^2 / mse)``, then the mean over the batch.  scikit-image is not
 installed in the build container: the oracle is a numpy/scipy restatement of that published algorithm and the
 parity with scikit-image itself is *unpinned*.
+
+``aster_metrics`` / ``gradient_strata`` (f5): the per-pair evaluation table of model_perf_aster_formatds.py:371-437 (PSNR,
+SSIM, RMSE, the three gradient-stratum RMSEs, GSSIM of utils.py:1904-2005, RMSE_grad), one (B,8) float64 row per pair.
 """
 from __future__ import annotations
 
 import torch
 
 from . import _lib
+from .sif_ops import _taps_c
 
 
 def psnr_ssim(predictions, targets):
@@ -37,3 +41,83 @@ def psnr_skimage(predictions, targets):
 def ssim_skimage(predictions, targets):
     """Drop-in for us.ssim_skimage on device tensors (returns a 0-d device tensor)."""
     return psnr_ssim(predictions, targets)[1]
+
+
+# ---- per-pair ASTER evaluation table (SURVEY.md §8 f5), model_perf_aster_formatds.py:371-437 ----------------------------
+# The column names of :507 without 'LPIPS' (out of scope: lpips.py fetches its weights from URLs).
+METRIC_NAMES = ("PSNR", "SSIM", "RMSE", "RMSE (low grad per image)", "RMSE (mean grad per image)",
+                "RMSE (high grad per image)", "GSSIM", "RMSE_grad")
+
+
+def _check_pairs(reference, prediction):
+    _lib.require_gpu(reference, "reference"); _lib.require_gpu(prediction, "prediction")
+    if reference.shape != prediction.shape or reference.dim() != 4 or reference.shape[1] != 1:
+        raise _lib.SifsrError("aster_metrics expects two (B,1,H,W) tensors of the same shape")
+    B, _, H, W = reference.shape
+    if H < 16 or W < 16:
+        raise _lib.SifsrError(f"aster_metrics needs H, W >= 16, got {H}x{W}")
+    return B, H, W
+
+
+def aster_metrics(reference, prediction, data_range=None):
+    """Per-pair evaluation metrics, columns ``METRIC_NAMES``, of model_perf_aster_formatds.py:371-437 on the device.
+
+    reference (ASTER, overlap_11) and prediction (overlap_22): (B,1,H,W) float32 device tensors, H, W >= 16 -> (B,8) float64
+    device tensor; no host synchronisation.  Or two lists of (H,W) / (1,H,W) / (1,1,H,W) device tensors of mixed sizes:
+    pairs of one shape run as one batch, rows come back in list order.
+
+    data_range None: per pair, R = max(a u b) - min(a u b) in float32 (:373-374), as the evaluation passes it to PSNR, SSIM
+    and GSSIM.  The strata RMSEs (:379-404) divide by N, not by the stratum size: the reference's
+    ``filter((0.0).__ne__, ...)`` runs on np.float32 elements, for which ``float.__ne__`` returns NotImplemented (truthy),
+    so nothing is filtered and the zeroed entries stay in the mean.
+    """
+    if isinstance(reference, (list, tuple)):
+        return _aster_metrics_list(reference, prediction, data_range)
+    B, H, W = _check_pairs(reference, prediction)
+    nbytes = _lib.call("sifsr_eval_metrics_scratch_bytes", B, H, W)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=reference.device)
+    out = torch.empty(B, 8, dtype=torch.float64, device=reference.device)
+    _lib.call("sifsr_eval_metrics", reference.detach(), prediction.detach(), B, H, W, _taps_c(0.1, 4, None),
+              -1.0 if data_range is None else float(data_range), scratch, nbytes, out, _lib.stream_ptr(reference.device))
+    return out
+
+
+def _as_hw(t, what):
+    if not isinstance(t, torch.Tensor):
+        raise _lib.SifsrError(f"{what} must be a device tensor")
+    if t.dim() > 2 and all(s == 1 for s in t.shape[:-2]):
+        t = t.reshape(t.shape[-2:])
+    if t.dim() != 2:
+        raise _lib.SifsrError(f"{what}: expected an (H,W), (1,H,W) or (1,1,H,W) image, got {tuple(t.shape)}")
+    return t
+
+
+def _aster_metrics_list(references, predictions, data_range):
+    if len(references) != len(predictions) or not references:
+        raise _lib.SifsrError("aster_metrics: two non-empty lists of the same length expected")
+    refs = [_as_hw(r, "reference") for r in references]
+    preds = [_as_hw(p, "prediction") for p in predictions]
+    groups = {}
+    for i, (r, p) in enumerate(zip(refs, preds)):
+        if r.shape != p.shape:
+            raise _lib.SifsrError(f"pair {i}: reference {tuple(r.shape)} and prediction {tuple(p.shape)} differ")
+        groups.setdefault(tuple(r.shape), []).append(i)
+    out = torch.empty(len(refs), 8, dtype=torch.float64, device=refs[0].device)
+    for idx in groups.values():
+        rows = aster_metrics(torch.stack([refs[i] for i in idx])[:, None], torch.stack([preds[i] for i in idx])[:, None],
+                             data_range)
+        out[torch.tensor(idx, device=out.device)] = rows
+    return out
+
+
+def gradient_strata(reference):
+    """The gradient strata of model_perf_aster_formatds.py:379-404 alone, (B,1,H,W) float32 device tensor ->
+    (g (B,1,H,W) = |ref - get_output_ftm(ref)|, q25 (B,), q75 (B,) = np.percentile(g, 25 / 75) per image (numpy 2.x 'linear'
+    in float32, exact order statistics), counts (B,3) int32 = #(g < q25), #(q25 <= g <= q75), #(g >= q75))."""
+    B, H, W = _check_pairs(reference, reference)
+    g = torch.empty_like(reference)
+    q = torch.empty(B, 2, dtype=torch.float32, device=reference.device)
+    counts = torch.empty(B, 3, dtype=torch.int32, device=reference.device)
+    _lib.call("sifsr_gradient_strata", reference.detach(), B, H, W, _taps_c(0.1, 4, None), g, q, counts,
+              _lib.stream_ptr(reference.device))
+    return g, q[:, 0], q[:, 1], counts

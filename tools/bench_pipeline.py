@@ -28,3 +28,11 @@ print(f"granule_to_tiles alone: {ms*1e3:.0f} us ({x.numel()*4/1e6:.0f} MB writte
 p = torch.randn(64, 1, 256, 256, device=dev); t = p + 0.1 * torch.randn_like(p)
 ms = timeit(lambda: sifsr.metrics.psnr_ssim(p, t), 20)
 print(f"psnr_ssim batch 64: {ms*1e3:.0f} us")
+# per-pair ASTER evaluation table (f5, model_perf_aster_formatds.py:371-437): B=64 at 256^2 and one 335x374 batch of 8.
+# The numpy / scipy restatement (tests/eval_reference.py) takes about 0.10 s per 256^2 pair and 0.20 s per 335x374 pair on one
+# CPU core of the build container.
+a = torch.randn(64, 1, 256, 256, device=dev).cumsum(2).cumsum(3) * 0.05 + 300; b = a + 0.4 * torch.randn_like(a)
+ms = timeit(lambda: sifsr.metrics.aster_metrics(a, b), 20)
+a2 = torch.randn(8, 1, 335, 374, device=dev).cumsum(2).cumsum(3) * 0.05 + 300; b2 = a2 + 0.4 * torch.randn_like(a2)
+ms2 = timeit(lambda: sifsr.metrics.aster_metrics(a2, b2), 20)
+print(f"aster_metrics batch 64 at 256x256: {ms*1e3:.0f} us ({ms*1e3/64:.1f} us/pair); batch 8 at 335x374: {ms2*1e3:.0f} us")
