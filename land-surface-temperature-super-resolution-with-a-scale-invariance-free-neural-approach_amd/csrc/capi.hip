@@ -262,7 +262,7 @@ int sifsr_conv3x3_wgrad_wino(const float* src0, int C0, const float* scale0, con
   if (!conv3x3_wgrad_use_wino(a, cin, cout)) return SIFSR_ERR_SHAPE;
   int rc = launch_conv3x3_wgrad_wino(a, cin, cout, nblk, S(stream));
   if (rc) return rc;
-  return launch_wgrad_reduce(scratch, nblk, cin, cout, wgrad_wino_nbi_chunk(a, cin), dw, S(stream));
+  return launch_wgrad_reduce(scratch, nblk, cin, cout, wgrad_wino_nbi_chunk(cin), dw, S(stream));
 }
 
 // Input gradient AND weight gradient of a 16 -> 16 channel layer from one read of its operands (conv_bwd16.hip).

@@ -86,7 +86,7 @@ int launch_wgrad_reduce_batched(const float* ws, const WgradReduceJob* jobs, int
 // Winograd F(3x3, 2x2) form of the weight gradient (conv_wgrad_wino.hip): same arguments and grid as launch_conv3x3_wgrad,
 // slabs of 16 * cin * cout floats per block; the finish call reduces the slabs (float64) and applies the output transform.
 bool conv3x3_wgrad_use_wino(const WgradArgs& a, int cin, int cout);
-int wgrad_wino_nbi_chunk(const WgradArgs& a, int cin);   // its Cin chunking (a 32-channel chunk may span the two sources)
+int wgrad_wino_nbi_chunk(int cin);   // its Cin chunking (a 32-channel chunk may span the two sources)
 int launch_conv3x3_wgrad_wino(const WgradArgs& a, int cin, int cout, int nblk, hipStream_t s);
 // Output transform of the Winograd F(3x3, 2x2) weight gradient, dW = A^T M A per (cout, cin) pair with A^T = [[1, .5, .5, 0],
 // [0, .5, -.5, 0], [0, .5, .5, 1]]: lane-local (a lane holds the same pairs for all 16 xi), applied by the producing kernels to their

@@ -21,7 +21,7 @@
 // per tile, and the two roles stage at different times (see tile_loop).  The replicate-border fold of the input gradient stays the separate kernel (dgrad_border_kernel).
 #include "conv.h"
 
-#include <stdlib.h>
+#include "switches.h"
 
 SIFSR_DIAG_CLOCK16_DECL   // (diag.h: nothing in the shipped build; tools/clock_probe16.py reads the per-phase clock sums)
 
@@ -534,16 +534,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bwd16_kernel(const Bwd16Args a
 }  // namespace
 
 bool conv3x3_bwd16_applies(int B, int H, int W) {
-  static const int off = getenv("SIFSR_NO_BWD16") ? atoi(getenv("SIFSR_NO_BWD16")) : 0;   // 1: separate input- / weight-gradient kernels (A/B)
-  return !off && B >= 1 && H >= 32 && W >= 32 && H % 16 == 0 && W % 16 == 0 && (size_t)B * H * W * 64 < ((size_t)1 << 32) - 4096;
+  return !sifsr_switches().no_bwd16 && B >= 1 && H >= 32 && W >= 32 && H % 16 == 0 && W % 16 == 0 && (size_t)B * H * W * 64 < ((size_t)1 << 32) - 4096;
 }
 
 int conv3x3_bwd16_grid(int B, int H, int W) {
   const int ntiles = B * (H / 16) * (W / 16);
-  static const int dbg_env = getenv("SIFSR_DBG_BWD16_GRID") ? atoi(getenv("SIFSR_DBG_BWD16_GRID")) : 256;   // one workgroup per CU
-  static const int dbg = dbg_env >= 1 ? dbg_env : 256;   // 0 / negative / unparsable: the default (the walk divides by it)
-  if (ntiles <= dbg) return ntiles;
-  const int rounds = (ntiles + dbg - 1) / dbg;
+  constexpr int gmax = 256;   // one workgroup per CU
+  if (ntiles <= gmax) return ntiles;
+  const int rounds = (ntiles + gmax - 1) / gmax;
   int g = (ntiles + rounds - 1) / rounds;
   g = (g + 7) & ~7;
   return g < ntiles ? g : ntiles;

@@ -24,7 +24,7 @@
 //     workgroup (deterministic 2-stage reduction), residual addend, split destinations.
 #include "conv.h"
 
-#include <stdlib.h>
+#include "switches.h"
 
 namespace {
 
@@ -1015,9 +1015,8 @@ __global__ __launch_bounds__(256, 8) void dgrad_border_kernel(const float* __res
 // Number of persistent workgroups (== rows of stat_partials written) for a B x H x W conv with cout outputs:
 // at most 256 CUs x the residency the kernel variant reaches, and an even split of the tiles.
 bool conv3x3_use_wino(const ConvArgs& a, int cout) {
-  static const int off = getenv("SIFSR_NO_WINO") ? atoi(getenv("SIFSR_NO_WINO")) : 0;   // 1: direct kernels everywhere (A/B, debugging)
   // (16 output channels: the kernel keeps the layer's transform-domain weights in LDS, two channel blocks at most)
-  return !off && a.wpack_wino != nullptr && a.bf16 == 0 && cout <= 64 && a.H % 2 == 0 && a.W % 2 == 0 && (cout > 16 || a.NQ <= 2);
+  return !sifsr_switches().no_wino && a.wpack_wino != nullptr && a.bf16 == 0 && cout <= 64 && a.H % 2 == 0 && a.W % 2 == 0 && (cout > 16 || a.NQ <= 2);
 }
 
 // 0: tap-domain kernel; 1: Winograd, one workgroup per CU; 2: Winograd forward with 16 output channels, two per CU
@@ -1030,8 +1029,7 @@ int conv3x3_grid_blocks(int B, int H, int W, int cout, int wino) {
   const int ntiles = B * ((H + 15) / 16) * ((W + 15) / 16);
   const int per_cu = wino ? (wino == 2 ? 2 : 1) : (cout >= 64 ? 1 : 2);   // residency of the kernel variants (VGPR-limited); wino == 2: the
                                                                             // two-workgroups-per-CU forward variant for 16 output channels
-  static const int dbg_grid = getenv("SIFSR_DBG_CONV_GRID") ? atoi(getenv("SIFSR_DBG_CONV_GRID")) : 0;   // tuning knob
-  const int gmax = dbg_grid > 0 ? dbg_grid : 256 * per_cu;
+  const int gmax = 256 * per_cu;
   if (ntiles <= gmax) return ntiles;
   const int rounds = (ntiles + gmax - 1) / gmax;
   int g = (ntiles + rounds - 1) / rounds;

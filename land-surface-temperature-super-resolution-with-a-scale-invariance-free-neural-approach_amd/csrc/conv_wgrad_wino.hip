@@ -25,8 +25,6 @@
 // wgrad_wino_finish applies A^T . A and scatters to the OIHW gradient.
 #include "conv.h"
 
-#include <stdlib.h>
-
 namespace {
 
 constexpr int XT_ROWS = 8;                 // tile rows (4 patch rows x 8 patch columns = 32 patches = 8 k-steps)
@@ -318,16 +316,12 @@ int launch_xw(const WgradArgs& a, int chunks, int halves, int nblk, hipStream_t 
 }  // namespace
 
 // 16-channel blocks per cin chunk (blockIdx.y): 32-channel chunks from 32 input channels on, also across the two sources
-int wgrad_wino_nbi_chunk(const WgradArgs& a, int cin) {
-  (void)a;
-  return cin < 32 ? 1 : 2;
-}
+int wgrad_wino_nbi_chunk(int cin) { return cin < 32 ? 1 : 2; }
 
 bool conv3x3_wgrad_use_wino(const WgradArgs& a, int cin, int cout) {
-  static const int off = getenv("SIFSR_NO_WINO_WGRAD") ? atoi(getenv("SIFSR_NO_WINO_WGRAD")) : 0;   // 1: tap-domain weight gradients (A/B)
-  const int nbo = cout / 16, nbi = wgrad_wino_nbi_chunk(a, cin);
+  const int nbo = cout / 16, nbi = wgrad_wino_nbi_chunk(cin);
   const bool shape = (nbo == 1 || nbo == 2 || nbo == 4) && (nbi == 1 || nbi == 2) && !(nbo == 4 && nbi == 1);
-  return !off && a.bf16 == 0 && a.H % 2 == 0 && a.W % 2 == 0 && shape;
+  return a.bf16 == 0 && a.H % 2 == 0 && a.W % 2 == 0 && shape;
 }
 
 int launch_conv3x3_wgrad_wino(const WgradArgs& a, int cin, int cout, int nblk, hipStream_t s) {
@@ -344,14 +338,12 @@ int launch_conv3x3_wgrad_wino(const WgradArgs& a, int cin, int cout, int nblk, h
   }
   const bool dyf = a.dy_y != nullptr;
   if (dyf && !a.dy_coef) return SIFSR_ERR_ARG;
-  const int nbi = wgrad_wino_nbi_chunk(a, cin), chunks = (cin / 16) / nbi, nbo = cout / 16;
-  static const int split64 = getenv("SIFSR_DBG_WGRAD_WINO_SPLIT64") ? atoi(getenv("SIFSR_DBG_WGRAD_WINO_SPLIT64")) : 1;   // A/B knob
+  const int nbi = wgrad_wino_nbi_chunk(cin), chunks = (cin / 16) / nbi, nbo = cout / 16;
 #define SIFSR_XW(NBOV, NBIV, HV)                                                                                     \
   if (nbo == NBOV * HV && nbi == NBIV)                                                                              \
     return dyf ? launch_xw<NBOV, NBIV, true>(a, chunks, HV, nblk, s) : launch_xw<NBOV, NBIV, false>(a, chunks, HV, nblk, s);
-  SIFSR_XW(1, 1, 1) SIFSR_XW(1, 2, 1) SIFSR_XW(2, 1, 1) SIFSR_XW(2, 2, 1)
-  if (split64) { SIFSR_XW(2, 2, 2) }
-  SIFSR_XW(4, 2, 1)
+  // 64 output channels run as two 32-channel halves (blockIdx.z): in one piece the kernel needs 436 registers, one workgroup per CU
+  SIFSR_XW(1, 1, 1) SIFSR_XW(1, 2, 1) SIFSR_XW(2, 1, 1) SIFSR_XW(2, 2, 1) SIFSR_XW(2, 2, 2)
 #undef SIFSR_XW
   return SIFSR_ERR_SHAPE;
 }

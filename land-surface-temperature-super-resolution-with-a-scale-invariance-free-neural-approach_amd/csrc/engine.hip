@@ -9,6 +9,7 @@
 //                dy_l = sc*g_l*[z>0] + k1*z + k0, z = y_l*sc + sh, is NEVER stored: formed while staging (bn_bwd4) by
 //                wgrad(a_in, g_l, y_l) -> slabs -> reduce -> dW  and  dgrad(g_l, y_l) (+ border fold) -> g of the inputs
 #include "engine.h"
+#include "switches.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -25,8 +26,30 @@ HalfStorageScope::HalfStorageScope(bool on) : prev(t_half_storage) { t_half_stor
 HalfStorageScope::~HalfStorageScope() { t_half_storage = prev; }
 
 // ---------------------------------------------------------------------------------------------
+// run-time switches (switches.h): the one place in the library that reads the environment
+// ---------------------------------------------------------------------------------------------
+static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+const Switches& sifsr_switches() {
+  static const Switches sw = {   // in the order of the struct's fields
+      env_int("SIFSR_WGRAD_STREAM", 1), env_int("SIFSR_WGRAD_WINO", 2),  env_int("SIFSR_NO_WINO", 0),
+      env_int("SIFSR_NO_WINO8", 0),     env_int("SIFSR_NO_BWD16", 0),    env_int("SIFSR_TAIL_APPLY", 0),
+      env_int("SIFSR_HEAD_LINEAR", 0),  env_int("SIFSR_BF16_BWD16", 0),  env_int("SIFSR_DBG_EARLY_REDUCE", 3),
+      env_int("SIFSR_DBG_POOL_ON_LOAD", 1)};
+  return sw;
+}
+
+// ---------------------------------------------------------------------------------------------
 // network table
 // ---------------------------------------------------------------------------------------------
+// encoder stage k (DownBlock_pool, model.py:528-531): pool(enc_prev) -> enc_a -> enc_b -> (+ residual) -> enc_c, pc channels
+static constexpr int enc_prev[3] = {L_IN3, L_D1C, L_D2C};
+static constexpr int enc_a[3] = {L_D1A, L_D2A, L_D3A}, enc_b[3] = {L_D1B, L_D2B, L_D3B}, enc_c[3] = {L_D1C, L_D2C, L_D3C};
+static constexpr int pc[3] = {16, 32, 64};
+// decoder stage k (UpBlock, model.py:235-248), output level 2 - k: cat([up2x(dec_low), dec_skip]) -> dec_a -> dec_b, uc upsampled channels
+static constexpr int dec_low[3] = {L_D3C, L_U1B, L_U2B}, dec_skip[3] = {L_D2C, L_D1C, L_IN3};
+static constexpr int dec_a[3] = {L_U1A, L_U2A, L_U3A}, dec_b[3] = {L_U1B, L_U2B, L_U3B};
+static constexpr int uc[3] = {64, 32, 16};
+
 static NetTable build_net() {
   static const int cin[SIFSR_NUM_BN_LAYERS] = {2, 16, 16, 16, 16, 32, 32, 32, 64, 64, 64, 128, 64, 64, 32, 32, 16};
   static const int cout[SIFSR_NUM_BN_LAYERS] = {16, 16, 16, 16, 32, 32, 32, 64, 64, 64, 64, 64, 32, 32, 16, 16, 16};
@@ -59,21 +82,15 @@ const NetTable& sifsr_net() {
 // ---------------------------------------------------------------------------------------------
 static size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }   // in floats (256 B)
 
-static int wgrad_blocks(int cin, int cout, int chunks, int ntiles, bool wino = false) {
-  // persistent, software-pipelined workgroups: two per CU are resident (four for the 16->16 variant: 20 KB LDS,
-  // 66 VGPRs), so launch that many in total (x-dim = total / Cin chunks in blockIdx.y), but keep >= 4 tiles per
-  // workgroup so that the slab write + slab reduction stay small next to the MFMA work (measured per layer).
-  // (re-swept with the weight gradients on the second stream: smaller grids leave the chain more room but lose more
-  // than they give -- 1024 / 512 stay)
-  static const int dbg_scale = getenv("SIFSR_DBG_WGRAD_GRID_PCT") ? atoi(getenv("SIFSR_DBG_WGRAD_GRID_PCT")) : 100;   // tuning knob
-  // (round 2, beside the Winograd chain -- one workgroup per CU, registers to spare: 1.5x the round-1 grids, +1 %; flat to 2.5x)
-  // Winograd-domain kernels (conv_wgrad_wino.hip): two workgroups per CU are resident (registers), every workgroup walks the same
-  // number of tiles -> exactly one round of resident workgroups
-  static const int dbg_wino = getenv("SIFSR_DBG_WGRAD_WINO_GRID") ? atoi(getenv("SIFSR_DBG_WGRAD_WINO_GRID")) : 512;
-  static const int dbg_wino11 = getenv("SIFSR_DBG_WGRAD_WINO_GRID11") ? atoi(getenv("SIFSR_DBG_WGRAD_WINO_GRID11")) : 512;
-  static const int dbg_wino42 = getenv("SIFSR_DBG_WGRAD_WINO_GRID42") ? atoi(getenv("SIFSR_DBG_WGRAD_WINO_GRID42")) : 256;   // 64 output channels: one resident workgroup per CU
-  const int wino_total = (cin == 16 && cout == 16) ? dbg_wino11 : cout == 64 ? dbg_wino42 : dbg_wino;
-  const int total = wino ? (wino_total > 768 ? 768 : wino_total) : ((cin == 16 && cout == 16) ? 1536 : 768) * dbg_scale / 100;
+// Workgroups (x-dim; the Cin chunks are in blockIdx.y) of a weight-gradient launch.  The kernels are persistent and
+// software-pipelined, so the grid is a fixed total, but every workgroup keeps >= 4 tiles so that the slab write + slab reduction
+// stay small next to the MFMA work (measured per layer).
+static int wgrad_blocks(int cin, int cout, int chunks, int ntiles, bool wino) {
+  // tap domain: 1.5 x the resident workgroups -- two per CU, four for the 16 -> 16 variant (20 KB LDS, 66 VGPRs) -- was +1 % beside the
+  // Winograd chain (flat to 2.5 x); re-swept with the weight gradients on the second stream: smaller grids lose more than they give
+  // Winograd domain (conv_wgrad_wino.hip): exactly one round of resident workgroups, each walking the same number of tiles -- two per
+  // CU (registers), one per CU for 64 output channels
+  const int total = wino ? (cout == 64 ? 256 : 512) : (cin == 16 && cout == 16 ? 1536 : 768);
   int n = total / chunks;
   if (n < 64) n = 64;
   const int cap = ntiles / 4 > 0 ? ntiles / 4 : 1;
@@ -98,12 +115,11 @@ int sifsr_layout(int B, int H, int W, int training, WsLayout* o) {
   w.wfwd = take(nt.total_wpack); w.wdg = take(4 * (size_t)nt.total_wpack);
   w.wwf = take((size_t)nt.total_wpack / 9 * 16); w.wwd = take((size_t)nt.total_wpack / 9 * 16);   // Winograd-domain packs
   for (int l = 0; l < SIFSR_NUM_BN_LAYERS; ++l) w.y[l] = take(nt.L[l].cout * N[nt.L[l].level]);
-  static const int pc[3] = {16, 32, 64};
   for (int k = 0; k < 3; ++k) {
     w.P[k] = take(pc[k] * N[k + 1]);
     w.R[k] = take(pc[k] * N[k + 1]);
   }
-  w.U[0] = take(64 * N[2]); w.U[1] = take(32 * N[1]); w.U[2] = take(16 * N[0]);
+  for (int k = 0; k < 3; ++k) w.U[k] = take(uc[k] * N[2 - k]);
 
   // scratch: BN statistic partials (forward: one entry per conv workgroup; backward: <= 1024 blocks)
   size_t maxpart = 0;
@@ -116,7 +132,7 @@ int sifsr_layout(int B, int H, int W, int training, WsLayout* o) {
   // ... and the upsample adjoints' rows (one per 8x8 low-resolution pixels and image) for the three decoder inputs
   for (int k = 0; k < 3; ++k) {
     const int lh = H >> (3 - k), lw = W >> (3 - k);
-    const size_t n = (size_t)up2x_bwd_stat_rows(B, lh, lw, 64 >> k) * (64 >> k) * 2;
+    const size_t n = (size_t)up2x_bwd_stat_rows(B, lh, lw, uc[k]) * uc[k] * 2;
     maxpart = n > maxpart ? n : maxpart;
   }
   w.partials = take(maxpart);
@@ -130,7 +146,7 @@ int sifsr_layout(int B, int H, int W, int training, WsLayout* o) {
     w.dy_border = take(16 * N[0]);   // the largest layer (16 channels at level 0 = 32 at level 1 = 64 at level 2)
     w.dyB[0] = w.dyB[1] = w.dyB[2] = w.dy_border;
     for (int k = 0; k < 3; ++k) w.gP[k] = take(pc[k] * N[k + 1]);
-    w.gU[0] = take(64 * N[2]); w.gU[1] = take(32 * N[1]); w.gU[2] = take(16 * N[0]);
+    for (int k = 0; k < 3; ++k) w.gU[k] = take(uc[k] * N[2 - k]);
     w.slabs = take(1024 * 288);   // edge-layer partials
     w.gram = take(conv_in_gram_scratch_floats());
     w.slab_l[0] = 0; w.slab_cap[0] = 0;
@@ -139,7 +155,7 @@ int sifsr_layout(int B, int H, int W, int training, WsLayout* o) {
       const int ntiles = B * ((lvh + 7) / 8) * ((lvw + 15) / 16);
       // upper bound over chunkings (x-dim blocks * chunks <= blocks at one chunk)
       // (9 values per weight pair: the Winograd F(3x3,2x2) kernels apply their output transform before they write a slab)
-      // ... and over the two kernel families: the tap-domain grid scales with SIFSR_DBG_WGRAD_GRID_PCT, the Winograd one does not
+      // ... and over the two kernel families: both can run for the same layer (SIFSR_WGRAD_WINO, odd sizes, bf16 mode)
       const int nb_tap = wgrad_blocks(nt.L[l].cin, nt.L[l].cout, 1, ntiles, false), nb_wino = wgrad_blocks(nt.L[l].cin, nt.L[l].cout, 1, ntiles, true);
       w.slab_cap[l] = (size_t)(nb_tap > nb_wino ? nb_tap : nb_wino) * 9 * nt.L[l].cin * nt.L[l].cout;
       // ... and the fused input + weight gradient kernel of the 16 -> 16 layers writes one slab per workgroup
@@ -166,22 +182,44 @@ struct Ctx {
   const float* params;
   int B, H, W;
   hipStream_t s;
-  WgradReduceJob* jobs = nullptr;   // backward: slab reductions deferred to one batched launch
-  int* njobs = nullptr;
-  bool wino_wgrads = false;         // backward: the Winograd-domain weight-gradient kernels (and the fused 16 -> 16 kernel) may run
   int bf16 = 0;                     // 1: bf16 MFMA operands (config 5)
-  struct SideLane* side = nullptr;  // backward: the weight gradients' own stream (nullptr = everything on s)
+  // backward only
+  float* grads = nullptr;
+  struct BwdState* bwd = nullptr;   // what the schedule accumulates while it is enqueued (below)
+  struct SideLane* side = nullptr;  // the weight gradients' own stream (nullptr = everything on s)
   bool* forked = nullptr;           // set once anything was enqueued on the side stream (SideLaneGuard)
   int lvH(int lv) const { return H >> lv; }
   int lvW(int lv) const { return W >> lv; }
   float* f(size_t off) const { return ws + off; }
-  const float* scale(int l) const { return ws + lay.scale + nt.L[l].ch_off; }
-  const float* shift(int l) const { return ws + lay.shift + nt.L[l].ch_off; }
+  // per-layer regions
+  float* y(int l) const { return ws + lay.y[l]; }
+  float* g(int l) const { return ws + lay.g[l]; }
+  float* mean(int l) const { return ws + lay.mean + nt.L[l].ch_off; }
+  float* invstd(int l) const { return ws + lay.invstd + nt.L[l].ch_off; }
+  float* scale(int l) const { return ws + lay.scale + nt.L[l].ch_off; }
+  float* shift(int l) const { return ws + lay.shift + nt.L[l].ch_off; }
+  float* coef_f(int l) const { return ws + lay.coef_f + 4 * (size_t)nt.L[l].ch_off; }        // bn_bwd4's [sc | sh | k1 | k0]
+  double* coef() const { return reinterpret_cast<double*>(ws + lay.coef); }                  // ... of the current layer, float64
+  float* slab(int l) const { return ws + lay.slab_l[l]; }
+  // weight packs of layer l.  Its part of the wdg region is [fp32 dgrad | fwd bf16 (n / 2 floats) | dgrad bf16 | unused], n = 9 * cin * cout
+  size_t wn(int l) const { return (size_t)9 * nt.L[l].cin * nt.L[l].cout; }
+  const float* w_dgrad_f32(int l) const { return ws + lay.wdg + 4 * (size_t)nt.L[l].wpack_off; }
+  const float* w_fwd(int l) const { return bf16 ? w_dgrad_f32(l) + wn(l) : ws + lay.wfwd + nt.L[l].wpack_off; }
+  const float* w_dgrad(int l) const { return bf16 ? w_dgrad_f32(l) + wn(l) + wn(l) / 2 : w_dgrad_f32(l); }
+  const float* w_fwd_wino(int l) const { return ws + lay.wwf + (size_t)nt.L[l].wpack_off / 9 * 16; }
+  const float* w_dgrad_wino(int l) const { return ws + lay.wwd + (size_t)nt.L[l].wpack_off / 9 * 16; }
+};
+
+struct BwdState {
+  WgradReduceJob jobs[16];   // slab reductions deferred to a batched launch (finish_wgrads)
+  int njobs = 0;
+  int last_fused = -1;       // the last layer whose slabs the fused 16 -> 16 kernel wrote on the CALLER's stream (its ev[] marks them
+                             // complete; recorded in enqueue order, so it covers every earlier one)
 };
 
 ConvSrc src_raw(const float* p, int C) { ConvSrc s; s.ptr = p; s.scale = nullptr; s.shift = nullptr; s.C = C; s.coff = 0; s.nq = C / 16; return s; }
 ConvSrc src_act(const Ctx& c, int l) {
-  ConvSrc s; s.ptr = c.f(c.lay.y[l]); s.scale = c.scale(l); s.shift = c.shift(l); s.C = c.nt.L[l].cout; s.coff = 0; s.nq = s.C / 16; return s;
+  ConvSrc s; s.ptr = c.y(l); s.scale = c.scale(l); s.shift = c.shift(l); s.C = c.nt.L[l].cout; s.coff = 0; s.nq = s.C / 16; return s;
 }
 ConvSrc src_none() { ConvSrc s; s.ptr = nullptr; s.scale = nullptr; s.shift = nullptr; s.C = 0; s.coff = 0; s.nq = 0; return s; }
 
@@ -212,8 +250,7 @@ struct SideLane {
 int g_side_override = -1;   // sifsr_engine_set_wgrad_stream: -1 = environment default
 
 SideLane* side_lane(hipStream_t main_stream) {
-  static const int env_default = getenv("SIFSR_WGRAD_STREAM") ? atoi(getenv("SIFSR_WGRAD_STREAM")) : 1;   // 0: single stream
-  if (!(g_side_override >= 0 ? g_side_override : env_default)) return nullptr;
+  if (!(g_side_override >= 0 ? g_side_override : sifsr_switches().wgrad_stream)) return nullptr;
   static std::mutex mu;
   static SideLane lanes[16];   // per device; events are re-recorded per call, so calls on different caller streams are
                                // safe as long as their enqueues do not interleave (SideLane::in_use, SideLaneGuard)
@@ -304,19 +341,25 @@ struct ProfScope {
   }
 };
 
+// training-mode BatchNorm of unit l from the nblk rows of statistic partials its convolution left: mean / invstd / scale / shift
+// and the running statistics
+int bn_unit_finalize(const Ctx& c, int l, int nblk, float* running, float momentum, float eps) {
+  const LayerInfo& L = c.nt.L[l];
+  return launch_bn_finalize(c.f(c.lay.partials), nblk, L.cout, (double)c.lay.npix[L.level], c.params + L.gamma_off,
+                            c.params + L.beta_off, running + L.run_off, running + L.run_off + L.cout, momentum, eps,
+                            c.mean(l), c.invstd(l), c.scale(l), c.shift(l), c.s);
+}
+
 // forward of one MFMA Conv(-BN) unit
 int conv_unit_fwd(const Ctx& c, int l, ConvSrc s0, ConvSrc s1, int training, float* running, float momentum, float eps) {
   const LayerInfo& L = c.nt.L[l];
   ConvArgs a;
   a.src[0] = s0; a.src[1] = s1;
-  a.dst[0].ptr = c.f(c.lay.y[l]); a.dst[0].C = L.cout; a.dst[0].coff = 0;
+  a.dst[0].ptr = c.y(l); a.dst[0].C = L.cout; a.dst[0].coff = 0;
   a.dst[1] = a.dst[0];
   a.bf16 = c.bf16;
-  {
-    const size_t n = (size_t)9 * L.cin * L.cout;   // bf16 packs live behind the layer's fp32 dgrad pack
-    a.wpack = a.bf16 ? c.f(c.lay.wdg) + 4 * (size_t)L.wpack_off + n : c.f(c.lay.wfwd) + L.wpack_off;
-  }
-  a.wpack_wino = c.f(c.lay.wwf) + (size_t)L.wpack_off / 9 * 16;
+  a.wpack = c.w_fwd(l);
+  a.wpack_wino = c.w_fwd_wino(l);
   a.addend = nullptr; a.addC = 0;
   a.stat_partials = training ? c.f(c.lay.partials) : nullptr;
   a.dst_split = L.cout / 16;
@@ -326,13 +369,8 @@ int conv_unit_fwd(const Ctx& c, int l, ConvSrc s0, ConvSrc s1, int training, flo
     ProfScope ps(l, 1, c.s);
     SIFSR_TRY(launch_conv3x3_mfma(a, L.cout, 0, c.s));
   }
-  if (training) {
-    const int nblk = conv3x3_grid_blocks(c.B, a.H, a.W, L.cout, conv3x3_wino_kind(a, L.cout, 0));
-    SIFSR_TRY(launch_bn_finalize(c.f(c.lay.partials), nblk, L.cout, (double)c.B * a.H * a.W, c.params + L.gamma_off,
-                                 c.params + L.beta_off, running + L.run_off, running + L.run_off + L.cout, momentum, eps,
-                                 c.f(c.lay.mean) + L.ch_off, c.f(c.lay.invstd) + L.ch_off,
-                                 c.f(c.lay.scale) + L.ch_off, c.f(c.lay.shift) + L.ch_off, c.s));
-  }
+  if (training)
+    SIFSR_TRY(bn_unit_finalize(c, l, conv3x3_grid_blocks(c.B, a.H, a.W, L.cout, conv3x3_wino_kind(a, L.cout, 0)), running, momentum, eps));
   return SIFSR_OK;
 }
 
@@ -344,72 +382,69 @@ int conv_unit_fwd(const Ctx& c, int l, ConvSrc s0, ConvSrc s1, int training, flo
 // layer above (conv_unit_dgrad with bn_layer), so the reduce pass over (g, y) is skipped.
 // border_rows: rows the border-fold kernel added to bpart (default: those of a 16-channel dgrad); 0 when the sums came
 // from the upsample adjoint (resample.hip), which has no border part.
-int bn_unit_bwd(const Ctx& c, int l, float* g, float* grads, const float* gp = nullptr, int fused_stats = 0, int border_rows = -1,
+int bn_bwd_reduce_blocks(size_t npix) {
+  const size_t nb = npix / 256;
+  return (int)(nb > 1024 ? 1024 : (nb < 1 ? 1 : nb));
+}
+int bn_unit_bwd(const Ctx& c, int l, const float* gp = nullptr, int fused_stats = 0, int border_rows = -1,
                 bool writeback = true) {   // writeback = false (with gp): the consumer adds the pooling adjoint itself while staging
   const LayerInfo& L = c.nt.L[l];
   const int lh = c.lvH(L.level), lw = c.lvW(L.level);
   const size_t npix = c.lay.npix[L.level];
-  float* coef_f = c.f(c.lay.coef_f) + 4 * (size_t)L.ch_off;
+  float* dgamma = c.grads + L.gamma_off, *dbeta = c.grads + L.beta_off;
   if (fused_stats > 0) {
     if (gp != nullptr) return SIFSR_ERR_ARG;
     return launch_bn_bwd_finalize2(c.f(c.lay.partials), fused_stats, c.f(c.lay.bpart), border_rows >= 0 ? border_rows : dgrad_border_waves(c.B, lh, lw, 16),
-                                   L.cout, (double)npix, c.scale(l), c.f(c.lay.mean) + L.ch_off,
-                                   c.f(c.lay.invstd) + L.ch_off, grads + L.gamma_off, grads + L.beta_off,
-                                   reinterpret_cast<double*>(c.f(c.lay.coef)), c.s, c.shift(l), c.params + L.beta_off, coef_f);
+                                   L.cout, (double)npix, c.scale(l), c.mean(l), c.invstd(l), dgamma, dbeta, c.coef(), c.s, c.shift(l),
+                                   c.params + L.beta_off, c.coef_f(l));
   }
-  size_t nb = npix / 256;
-  const int nblk = (int)(nb > 1024 ? 1024 : (nb < 1 ? 1 : nb));
-  SIFSR_TRY(launch_bn_bwd_reduce(g, c.f(c.lay.y[l]), c.scale(l), c.shift(l), c.f(c.lay.mean) + L.ch_off, c.f(c.lay.invstd) + L.ch_off,
-                                 L.cout, npix, c.f(c.lay.partials), nblk, c.s, gp, lh, lw, (gp && writeback) ? g : nullptr));
-  return launch_bn_bwd_finalize(c.f(c.lay.partials), nblk, L.cout, (double)npix, c.scale(l), c.f(c.lay.mean) + L.ch_off,
-                                c.f(c.lay.invstd) + L.ch_off, grads + L.gamma_off, grads + L.beta_off,
-                                reinterpret_cast<double*>(c.f(c.lay.coef)), c.s, c.shift(l), c.params + L.beta_off, coef_f);
+  const int nblk = bn_bwd_reduce_blocks(npix);
+  SIFSR_TRY(launch_bn_bwd_reduce(c.g(l), c.y(l), c.scale(l), c.shift(l), c.mean(l), c.invstd(l), L.cout, npix, c.f(c.lay.partials), nblk,
+                                 c.s, gp, lh, lw, (gp && writeback) ? c.g(l) : nullptr));
+  return launch_bn_bwd_finalize(c.f(c.lay.partials), nblk, L.cout, (double)npix, c.scale(l), c.mean(l), c.invstd(l), dgamma, dbeta,
+                                c.coef(), c.s, c.shift(l), c.params + L.beta_off, c.coef_f(l));
 }
 
-static bool wgrad_wino_policy(int cin, int cout) {
-  // SIFSR_WGRAD_WINO: 0 = tap-domain kernels, 1 = Winograd up to 32 output channels, 2 = every layer (default; +5 % on the step)
-  static const int mode = getenv("SIFSR_WGRAD_WINO") ? atoi(getenv("SIFSR_WGRAD_WINO")) : 2;
-  (void)cin;
+// SIFSR_WGRAD_WINO (switches.h): the Winograd-domain weight-gradient kernels for a layer with cout output channels?
+static bool wgrad_wino_policy(int cout) {
+  const int mode = sifsr_switches().wgrad_wino;
   return mode == 2 || (mode == 1 && cout <= 32);
 }
 
 // weight gradient of MFMA unit l from its forward inputs and dy
 // dy_stored: `dy` is dL/dy_l itself (ub3.convbloc.bloc.3, written by the fused tail); otherwise it is g_l and dL/dy_l is
 // formed while staging from (g_l, y_l, the coefficients bn_unit_bwd left)
-int conv_unit_wgrad(const Ctx& c, int l, ConvSrc s0, ConvSrc s1, const float* dy, float* grads, bool dy_stored = false) {
+// The slabs are reduced later (finish_wgrads); with the second stream the kernel runs there, behind ev[l].
+int conv_unit_wgrad(const Ctx& c, int l, ConvSrc s0, ConvSrc s1, const float* dy, bool dy_stored = false) {
   const LayerInfo& L = c.nt.L[l];
   WgradArgs a;
   a.src[0] = s0; a.src[1] = s1;
-  a.dy = dy; a.slabs = c.f(c.lay.slab_l[l]);
-  if (!dy_stored) { a.dy_y = c.f(c.lay.y[l]); a.dy_coef = c.f(c.lay.coef_f) + 4 * (size_t)L.ch_off; }
+  a.dy = dy; a.slabs = c.slab(l);
+  if (!dy_stored) { a.dy_y = c.y(l); a.dy_coef = c.coef_f(l); }
   a.B = c.B; a.H = c.lvH(L.level); a.W = c.lvW(L.level);
   a.NQ = L.cin / 16;
   a.ntiles = c.B * ((a.H + 7) / 8) * ((a.W + 15) / 16);
   a.bf16 = c.bf16;
   // Winograd F(3x3,2x2) where it is the faster form (measured per shape, tools/sweep_layers.sh)
-  const bool wino = c.wino_wgrads && wgrad_wino_policy(L.cin, L.cout) && conv3x3_wgrad_use_wino(a, L.cin, L.cout);
-  const int nbi = wino ? wgrad_wino_nbi_chunk(a, L.cin) : wgrad_nbi_chunk(a, L.cin);
+  const bool wino = wgrad_wino_policy(L.cout) && conv3x3_wgrad_use_wino(a, L.cin, L.cout);
+  const int nbi = wino ? wgrad_wino_nbi_chunk(L.cin) : wgrad_nbi_chunk(a, L.cin);
   const int nblk = wgrad_blocks(L.cin, L.cout, L.cin / (16 * nbi), a.ntiles, wino);
   // every workgroup (x cin chunks) writes one slab of (16 | 9) * cin_chunk * cout floats into this layer's region
   if ((size_t)nblk * (L.cin / (16 * nbi)) * 9 * (16 * nbi) * L.cout > c.lay.slab_cap[l]) return SIFSR_ERR_WORKSPACE;
   hipStream_t ws = c.s;
-  if (c.side != nullptr && c.jobs != nullptr) {   // dy_l is complete on the main stream at this point
+  if (c.side != nullptr) {   // dy_l is complete on the main stream at this point
     if (hipEventRecord(c.side->ev[l], c.s) != hipSuccess || hipStreamWaitEvent(c.side->s, c.side->ev[l], 0) != hipSuccess)
       return SIFSR_ERR_ARG;
     ws = c.side->s;
-    if (c.forked) *c.forked = true;
+    *c.forked = true;
   }
   {
     ProfScope ps(l, 3, ws);
     if (wino) SIFSR_TRY(launch_conv3x3_wgrad_wino(a, L.cin, L.cout, nblk, ws));
     else SIFSR_TRY(launch_conv3x3_wgrad(a, L.cin, L.cout, nblk, ws));
   }
-  if (c.jobs != nullptr) {
-    WgradReduceJob& j = c.jobs[(*c.njobs)++];   // (both kernel families leave tap-domain slabs)
-    j.slab_off = c.lay.slab_l[l]; j.nblk = nblk; j.cin = L.cin; j.cout = L.cout; j.nbi_chunk = nbi; j.w_off = L.w_off;
-  } else {
-    SIFSR_TRY(launch_wgrad_reduce(a.slabs, nblk, L.cin, L.cout, nbi, grads + L.w_off, c.s));
-  }
+  WgradReduceJob& j = c.bwd->jobs[c.bwd->njobs++];   // (both kernel families leave tap-domain slabs)
+  j.slab_off = c.lay.slab_l[l]; j.nblk = nblk; j.cin = L.cin; j.cout = L.cout; j.nbi_chunk = nbi; j.w_off = L.w_off;
   return SIFSR_OK;
 }
 
@@ -429,18 +464,14 @@ int conv_unit_dgrad(const Ctx& c, int l, const float* dy, float* g0, int C0, int
   a.src[0] = src_raw(dy, L.cout); a.src[1] = src_none();
   const float* dy_edge = dy;   // what the border-fold kernel reads (border pixels only)
   if (!dy_stored) {
-    a.bw_y = c.f(c.lay.y[l]); a.bw_coef = c.f(c.lay.coef_f) + 4 * (size_t)L.ch_off; a.bw_border = c.f(c.lay.dy_border);
+    a.bw_y = c.y(l); a.bw_coef = c.coef_f(l); a.bw_border = c.f(c.lay.dy_border);
     dy_edge = a.bw_border;
   }
   a.dst[0].ptr = g0; a.dst[0].C = C0; a.dst[0].coff = 0;
   a.dst[1].ptr = g1 ? g1 : g0; a.dst[1].C = g1 ? C1 : C0; a.dst[1].coff = 0;
   a.bf16 = c.bf16;
-  const float* wdg_f32 = c.f(c.lay.wdg) + 4 * (size_t)L.wpack_off;
-  {
-    const size_t n = (size_t)9 * L.cin * L.cout;
-    a.wpack = a.bf16 ? wdg_f32 + n + n / 2 : wdg_f32;   // [fp32 dgrad | fwd bf16 (n/2 floats) | dgrad bf16 | unused]
-  }
-  a.wpack_wino = c.f(c.lay.wwd) + (size_t)L.wpack_off / 9 * 16;
+  a.wpack = c.w_dgrad(l);
+  a.wpack_wino = c.w_dgrad_wino(l);
   a.addend = addend; a.addC = L.cin;
   a.stat_partials = nullptr;
   a.dst_split = split_ch / 16;
@@ -448,14 +479,14 @@ int conv_unit_dgrad(const Ctx& c, int l, const float* dy, float* g0, int C0, int
   a.NQ = L.cout / 16;
   if (fuse) {
     a.stat_partials = c.f(c.lay.partials);
-    a.bn_y = c.f(c.lay.y[bn_layer]); a.bn_scale = c.scale(bn_layer); a.bn_shift = c.shift(bn_layer);
+    a.bn_y = c.y(bn_layer); a.bn_scale = c.scale(bn_layer); a.bn_shift = c.shift(bn_layer);
     if (stat_rows) *stat_rows = conv3x3_grid_blocks(c.B, a.H, a.W, L.cin, conv3x3_wino_kind(a, L.cin, 1));
   }
   {
     ProfScope ps(l, 2, c.s);
     SIFSR_TRY(launch_conv3x3_mfma(a, L.cin, 1, c.s));
   }
-  SIFSR_TRY(launch_dgrad_border_fix(dy_edge, L.cout, wdg_f32, L.cin, g0, C0, split_ch, g1 ? g1 : g0, g1 ? C1 : C0, c.B, a.H,
+  SIFSR_TRY(launch_dgrad_border_fix(dy_edge, L.cout, c.w_dgrad_f32(l), L.cin, g0, C0, split_ch, g1 ? g1 : g0, g1 ? C1 : C0, c.B, a.H,
                                     a.W, c.s, c.bf16, fuse ? a.bn_y : nullptr, fuse ? a.bn_scale : nullptr,
                                     fuse ? a.bn_shift : nullptr, fuse ? c.f(c.lay.bpart) : nullptr));
   return SIFSR_OK;
@@ -466,14 +497,13 @@ int conv_unit_dgrad(const Ctx& c, int l, const float* dy, float* g0, int C0, int
 // layer (s0 = the forward input, 16 channels; gin = the gradient w.r.t. it, `addend` added; bn_layer as conv_unit_dgrad).
 // Returns SIFSR_OK with *applied = false when the separate kernels have to run instead (other shapes, bf16 mode, switched off).
 // The kernel runs on the CALLER's stream (it is part of the serial chain); its weight-gradient slabs join the Winograd
-// reduction list, and ev[l] of the second stream's lane marks their completion for a reduction issued there.
+// reduction list, and ev[l] of the second stream's lane marks their completion for a reduction issued there (BwdState::last_fused).
 bool bwd16_usable(const Ctx& c, int l, ConvSrc s0) {
   const LayerInfo& L = c.nt.L[l];
   // bf16 mode: the fused kernel exists for bf16 STORAGE too (fp32 Winograd arithmetic on widened values), but there it LOSES:
   // 14,450 against 15,900 patches/s on the bf16 step -- with half the bytes its fp32 matrix + transform work is the bottleneck,
   // while the separate bf16 kernels contract with 16x cheaper MFMAs.  SIFSR_BF16_BWD16=1 selects it for A/B.
-  static const int bf16_fused = getenv("SIFSR_BF16_BWD16") ? atoi(getenv("SIFSR_BF16_BWD16")) : 0;
-  return L.cin == 16 && L.cout == 16 && (c.bf16 == 0 || bf16_fused) && c.wino_wgrads && wgrad_wino_policy(16, 16) && s0.C == 16 &&
+  return L.cin == 16 && L.cout == 16 && (c.bf16 == 0 || sifsr_switches().bf16_bwd16) && wgrad_wino_policy(16) && s0.C == 16 &&
          s0.coff == 0 && conv3x3_bwd16_applies(c.B, c.lvH(L.level), c.lvW(L.level));
 }
 // dy_mode 0: `dy` is dL/dy itself.  1: `dy` is g = dL/d relu(bn(y_l)), dL/dy formed while staging.  2 (l = ub3.convbloc.bloc.3): `dy` is
@@ -493,14 +523,14 @@ int conv_unit_bwd16(const Ctx& c, int l, ConvSrc s0, const float* dy, float* gin
   a.x = s0.ptr; a.x_scale = s0.scale; a.x_shift = s0.shift;
   if (dy_mode == 2) { a.tail_dsr = dy; a.tail_w = c.params + c.nt.out_w_off; }
   else a.g = dy;
-  if (!dy_stored) { a.y = c.f(c.lay.y[l]); a.coef = c.f(c.lay.coef_f) + 4 * (size_t)L.ch_off; a.dy_border = c.f(c.lay.dy_border); }
-  a.wpack_wino = c.f(c.lay.wwd) + (size_t)L.wpack_off / 9 * 16;
+  if (!dy_stored) { a.y = c.y(l); a.coef = c.coef_f(l); a.dy_border = c.f(c.lay.dy_border); }
+  a.wpack_wino = c.w_dgrad_wino(l);
   a.gin = gin; a.addend = addend;
   if (fuse) {
-    a.bn_y = c.f(c.lay.y[bn_layer]); a.bn_scale = c.scale(bn_layer); a.bn_shift = c.shift(bn_layer); a.stat_partials = c.f(c.lay.partials);
+    a.bn_y = c.y(bn_layer); a.bn_scale = c.scale(bn_layer); a.bn_shift = c.shift(bn_layer); a.stat_partials = c.f(c.lay.partials);
     if (stat_rows) *stat_rows = grid;
   }
-  a.slabs = c.f(c.lay.slab_l[l]);
+  a.slabs = c.slab(l);
   a.B = c.B; a.H = lh; a.W = lw;
   a.half = c.bf16;
   if (store_dz && !fuse) return SIFSR_ERR_ARG;
@@ -510,15 +540,45 @@ int conv_unit_bwd16(const Ctx& c, int l, ConvSrc s0, const float* dy, float* gin
     ProfScope ps(l, 2, c.s);     // one launch = both passes of the layer: timed as its input-gradient selection
     SIFSR_TRY(launch_conv3x3_bwd16(a, c.s));
   }
-  const float* wdg_f32 = c.f(c.lay.wdg) + 4 * (size_t)L.wpack_off;
-  SIFSR_TRY(launch_dgrad_border_fix(dy_stored ? dy : a.dy_border, 16, wdg_f32, 16, gin, 16, 16, gin, 16, c.B, lh, lw, c.s, c.bf16,
+  SIFSR_TRY(launch_dgrad_border_fix(dy_stored ? dy : a.dy_border, 16, c.w_dgrad_f32(l), 16, gin, 16, 16, gin, 16, c.B, lh, lw, c.s, c.bf16,
                                     fuse ? a.bn_y : nullptr, fuse ? a.bn_scale : nullptr, fuse ? a.bn_shift : nullptr,
                                     fuse ? c.f(c.lay.bpart) : nullptr, a.store_dz));
-  WgradReduceJob& j = c.jobs[(*c.njobs)++];
+  WgradReduceJob& j = c.bwd->jobs[c.bwd->njobs++];
   j.slab_off = c.lay.slab_l[l]; j.nblk = grid; j.cin = 16; j.cout = 16; j.nbi_chunk = 1; j.w_off = L.w_off;
   if (c.side != nullptr && hipEventRecord(c.side->ev[l], c.s) != hipSuccess) return SIFSR_ERR_ARG;   // slabs of l complete
+  c.bwd->last_fused = l;
   *applied = true;
   return SIFSR_OK;
+}
+
+// Backward of MFMA unit l whose forward input is the one source s0: the fused 16 -> 16 kernel where it applies, otherwise the weight
+// gradient, then the input gradient.  gin (cin channels) = the gradient w.r.t. s0, `addend` added; bn_layer / stat_rows as
+// conv_unit_dgrad; dy_mode as conv_unit_bwd16 (mode 2 exists in the fused kernel only).
+int conv_unit_bwd(const Ctx& c, int l, ConvSrc s0, const float* dy, float* gin, const float* addend, int bn_layer, int* stat_rows,
+                  int dy_mode = 1) {
+  bool fused = false;
+  SIFSR_TRY(conv_unit_bwd16(c, l, s0, dy, gin, addend, bn_layer, stat_rows, dy_mode, &fused));
+  if (fused) return SIFSR_OK;
+  const int cin = c.nt.L[l].cin;
+  SIFSR_TRY(conv_unit_wgrad(c, l, s0, src_none(), dy, dy_mode == 0));
+  return conv_unit_dgrad(c, l, dy, gin, cin, cin, nullptr, 0, addend, bn_layer, stat_rows, dy_mode == 0);
+}
+
+// all pending weight-gradient slabs -> OIHW gradients, one launch on `st`
+int finish_wgrads(const Ctx& c, hipStream_t st) {
+  BwdState& b = *c.bwd;
+  if (b.njobs > 0) SIFSR_TRY(launch_wgrad_reduce_batched(c.ws, b.jobs, b.njobs, c.grads, st));
+  b.njobs = 0;
+  return SIFSR_OK;
+}
+// ... on the second stream, behind its own weight gradients and the fused 16 -> 16 kernels' slabs (written on the caller's stream).
+// It writes only the conv-weight regions of `grads`, which nothing on the caller's stream touches.
+int finish_wgrads_side(const Ctx& c) {
+  if (c.bwd->last_fused >= 0) {
+    if (hipStreamWaitEvent(c.side->s, c.side->ev[c.bwd->last_fused], 0) != hipSuccess) return SIFSR_ERR_ARG;
+    *c.forked = true;
+  }
+  return finish_wgrads(c, c.side->s);
 }
 
 }  // namespace
@@ -548,45 +608,32 @@ int sifsr_engine_forward(const float* x, float* sr, const float* params, float* 
   }
 
   // inbloc (DoubleConvolution, model.py:596)
-  {
-    const LayerInfo& L = nt.L[L_IN0];
-    SIFSR_TRY(launch_conv_in_fwd(x, params + L.w_off, c.f(w.y[L_IN0]), training ? c.f(w.partials) : nullptr, B, H, W, s));
-    if (training)
-      SIFSR_TRY(launch_bn_finalize(c.f(w.partials), conv_in_fwd_blocks(B, H, W), 16, (double)B * H * W, params + L.gamma_off,
-                                   params + L.beta_off, running + L.run_off, running + L.run_off + 16, momentum, eps,
-                                   c.f(w.mean) + L.ch_off, c.f(w.invstd) + L.ch_off, c.f(w.scale) + L.ch_off,
-                                   c.f(w.shift) + L.ch_off, s));
-  }
+  SIFSR_TRY(launch_conv_in_fwd(x, params + nt.L[L_IN0].w_off, c.y(L_IN0), training ? c.f(w.partials) : nullptr, B, H, W, s));
+  if (training) SIFSR_TRY(bn_unit_finalize(c, L_IN0, conv_in_fwd_blocks(B, H, W), running, momentum, eps));
   SIFSR_TRY(conv_unit_fwd(c, L_IN3, src_act(c, L_IN0), src_none(), training, running, momentum, eps));
 
   // encoder: DownBlock_pool x3 (model.py:597-599, :528-531)
-  static const int enc_prev[3] = {L_IN3, L_D1C, L_D2C};
-  static const int enc_a[3] = {L_D1A, L_D2A, L_D3A}, enc_b[3] = {L_D1B, L_D2B, L_D3B}, enc_c[3] = {L_D1C, L_D2C, L_D3C};
-  static const int pc[3] = {16, 32, 64};
   for (int k = 0; k < 3; ++k) {
     const int lp = enc_prev[k];
-    SIFSR_TRY(launch_bnrelu_pool2(c.f(w.y[lp]), c.scale(lp), c.shift(lp), c.f(w.P[k]), B, c.lvH(k), c.lvW(k), pc[k], s));
+    SIFSR_TRY(launch_bnrelu_pool2(c.y(lp), c.scale(lp), c.shift(lp), c.f(w.P[k]), B, c.lvH(k), c.lvW(k), pc[k], s));
     SIFSR_TRY(conv_unit_fwd(c, enc_a[k], src_raw(c.f(w.P[k]), pc[k]), src_none(), training, running, momentum, eps));
     SIFSR_TRY(conv_unit_fwd(c, enc_b[k], src_act(c, enc_a[k]), src_none(), training, running, momentum, eps));
-    SIFSR_TRY(launch_bnrelu_add(c.f(w.P[k]), c.f(w.y[enc_b[k]]), c.scale(enc_b[k]), c.shift(enc_b[k]), c.f(w.R[k]), pc[k],
+    SIFSR_TRY(launch_bnrelu_add(c.f(w.P[k]), c.y(enc_b[k]), c.scale(enc_b[k]), c.shift(enc_b[k]), c.f(w.R[k]), pc[k],
                                 w.npix[k + 1], s));
     SIFSR_TRY(conv_unit_fwd(c, enc_c[k], src_raw(c.f(w.R[k]), pc[k]), src_none(), training, running, momentum, eps));
   }
 
   // decoder: UpBlock x3 (model.py:601-603, :235-248); cat([up, skip], 1)
-  static const int dec_low[3] = {L_D3C, L_U1B, L_U2B}, dec_skip[3] = {L_D2C, L_D1C, L_IN3};
-  static const int dec_a[3] = {L_U1A, L_U2A, L_U3A}, dec_b[3] = {L_U1B, L_U2B, L_U3B};
-  static const int uc[3] = {64, 32, 16};
   for (int k = 0; k < 3; ++k) {
     const int lv = 2 - k;   // output level of this UpBlock
     const int ll = dec_low[k];
-    SIFSR_TRY(launch_bnrelu_up2x(c.f(w.y[ll]), c.scale(ll), c.shift(ll), c.f(w.U[k]), B, c.lvH(lv + 1), c.lvW(lv + 1), uc[k], s));
+    SIFSR_TRY(launch_bnrelu_up2x(c.y(ll), c.scale(ll), c.shift(ll), c.f(w.U[k]), B, c.lvH(lv + 1), c.lvW(lv + 1), uc[k], s));
     SIFSR_TRY(conv_unit_fwd(c, dec_a[k], src_raw(c.f(w.U[k]), uc[k]), src_act(c, dec_skip[k]), training, running, momentum, eps));
     SIFSR_TRY(conv_unit_fwd(c, dec_b[k], src_act(c, dec_a[k]), src_none(), training, running, momentum, eps));
   }
 
   // outlay (model.py:605)
-  SIFSR_TRY(launch_conv_out_fwd(c.f(w.y[L_U3B]), c.scale(L_U3B), c.shift(L_U3B), params + nt.out_w_off,
+  SIFSR_TRY(launch_conv_out_fwd(c.y(L_U3B), c.scale(L_U3B), c.shift(L_U3B), params + nt.out_w_off,
                                 params + nt.out_b_off, sr, B, H, W, s));
   return SIFSR_OK;
 }
@@ -605,14 +652,9 @@ int sifsr_engine_backward(const float* x, const float* dsr, const float* params,
   if (ws_floats < c.lay.total) return SIFSR_ERR_WORKSPACE;
   const NetTable& nt = c.nt;
   const WsLayout& w = c.lay;
-  WgradReduceJob jobs[16];
-  int njobs = 0;
-  c.jobs = jobs; c.njobs = &njobs;
-  c.wino_wgrads = true;
-  auto finish_wgrads = [&](hipStream_t st) -> int {
-    if (njobs > 0) SIFSR_TRY(launch_wgrad_reduce_batched(ws, jobs, njobs, grads, st));
-    return SIFSR_OK;
-  };
+  const Switches& sw = sifsr_switches();
+  BwdState state;
+  c.grads = grads; c.bwd = &state;
   // tiny problems are launch-latency-bound: the 17 event hand-offs cost more than the overlap returns (batch 1 at 256x256:
   // 1.67 ms with the second stream, 1.56 without; batch 4: 1.72 against 1.81)
   c.side = (size_t)B * H * W >= 2u * 65536u || g_side_override == 1 ? side_lane(s) : nullptr;
@@ -624,8 +666,7 @@ int sifsr_engine_backward(const float* x, const float* dsr, const float* params,
   // now; D needs dz of inbloc.bloc.0, which the fused kernel of inbloc.bloc.3 stores in place of g.  One 16-channel tensor less to
   // read (the D pass: 75 us against 136 us for the fused head kernel, stand-alone), but the Gram kernel costs 93 us of vector
   // issue beside the chain's first kernels: 10,390 against 10,420 patches/s on the step (same device, interleaved) -- not adopted.
-  static const int head_linear_env = getenv("SIFSR_HEAD_LINEAR") ? atoi(getenv("SIFSR_HEAD_LINEAR")) : 0;
-  const bool head_linear = head_linear_env != 0 && bwd16_usable(c, L_IN3, src_act(c, L_IN0));
+  const bool head_linear = sw.head_linear != 0 && bwd16_usable(c, L_IN3, src_act(c, L_IN0));
   if (head_linear) {
     hipStream_t gs = s;
     if (c.side != nullptr) {
@@ -636,171 +677,124 @@ int sifsr_engine_backward(const float* x, const float* dsr, const float* params,
     SIFSR_TRY(launch_conv_in_gram(x, c.f(w.gram), B, H, W, gs));
     if (c.side != nullptr && hipEventRecord(c.side->aux, gs) != hipSuccess) return SIFSR_ERR_ARG;
   }
-  static const int tail_apply_forced = getenv("SIFSR_TAIL_APPLY") ? atoi(getenv("SIFSR_TAIL_APPLY")) : 0;   // 1: keep the separate second pass (A/B)
-  bool tail_in_bwd16 = false;
   // outlay backward fused with the BatchNorm+ReLU backward of ub3.convbloc.bloc.3 (fused_edges.hip): the outlay
   // input gradient is recomputed from dsr in both passes instead of being stored; dy(L_U3B) -> g[L_U3B]
+  // With the fused 16 -> 16 backward kernel the second pass is part of that kernel's staging (conv_bwd16.hip, mode 2);
+  // SIFSR_TAIL_APPLY=1 keeps the separate pass (A/B)
+  const bool tail_in_bwd16 = !sw.tail_apply && bwd16_usable(c, L_U3B, src_act(c, L_U3A));
   {
     const LayerInfo& L = nt.L[L_U3B];
     int nblk = B * ((H + 15) / 16) * ((W + 15) / 16);
     if (nblk > 768) nblk = 768;   // persistent: three 168-register workgroups per CU (fused_edges.hip)
-    const float* y = c.f(w.y[L_U3B]);
-    SIFSR_TRY(launch_tail_bwd_reduce(y, c.scale(L_U3B), c.shift(L_U3B), c.f(w.mean) + L.ch_off, c.f(w.invstd) + L.ch_off, dsr,
+    SIFSR_TRY(launch_tail_bwd_reduce(c.y(L_U3B), c.scale(L_U3B), c.shift(L_U3B), c.mean(L_U3B), c.invstd(L_U3B), dsr,
                                      params + nt.out_w_off, c.f(w.slabs), c.f(w.partials), nblk, B, H, W, s));
     if (grads + nt.out_b_off != grads + nt.out_w_off + 144) return SIFSR_ERR_ARG;
-    // with the fused 16 -> 16 backward kernel the second pass is part of that kernel's staging (conv_bwd16.hip, mode 2)
-    tail_in_bwd16 = !tail_apply_forced && bwd16_usable(c, L_U3B, src_act(c, L_U3A));
-    SIFSR_TRY(launch_bn_bwd_finalize(c.f(w.partials), nblk, 16, (double)w.npix[0], c.scale(L_U3B), c.f(w.mean) + L.ch_off,
-                                     c.f(w.invstd) + L.ch_off, grads + L.gamma_off, grads + L.beta_off,
-                                     reinterpret_cast<double*>(c.f(w.coef)), s, c.shift(L_U3B), params + L.beta_off,
-                                     c.f(w.coef_f) + 4 * (size_t)L.ch_off, c.f(w.slabs), 145, grads + nt.out_w_off));   // (+ outlay dW / db)
+    SIFSR_TRY(launch_bn_bwd_finalize(c.f(w.partials), nblk, 16, (double)w.npix[0], c.scale(L_U3B), c.mean(L_U3B), c.invstd(L_U3B),
+                                     grads + L.gamma_off, grads + L.beta_off, c.coef(), s, c.shift(L_U3B), params + L.beta_off,
+                                     c.coef_f(L_U3B), c.f(w.slabs), 145, grads + nt.out_w_off));   // (+ outlay dW / db)
     if (!tail_in_bwd16)
-      SIFSR_TRY(launch_tail_bwd_apply(y, c.scale(L_U3B), c.shift(L_U3B), reinterpret_cast<const double*>(c.f(w.coef)), dsr,
-                                      params + nt.out_w_off, c.f(w.g[L_U3B]), B, H, W, s));
+      SIFSR_TRY(launch_tail_bwd_apply(c.y(L_U3B), c.scale(L_U3B), c.shift(L_U3B), c.coef(), dsr, params + nt.out_w_off, c.g(L_U3B),
+                                      B, H, W, s));
   }
 
   // decoder, last to first
-  static const int dec_low[3] = {L_D3C, L_U1B, L_U2B}, dec_skip[3] = {L_D2C, L_D1C, L_IN3};
-  static const int dec_a[3] = {L_U1A, L_U2A, L_U3A}, dec_b[3] = {L_U1B, L_U2B, L_U3B};
-  static const int uc[3] = {64, 32, 16};
   // the upsample adjoint that completes g of a low-resolution layer also leaves that layer's BatchNorm-backward sums (one
   // row per workgroup): up_rows > 0 tells the next bn_unit_bwd of that layer to skip its reduce pass
   int up_rows = 0;
-  int last_fused = -1;   // the last layer (decoder, encoder or inbloc) whose slabs the fused 16 -> 16 kernel wrote on the caller's stream (its ev[] marks them complete)
   for (int k = 2; k >= 0; --k) {
     const int lv = 2 - k;
     const int la = dec_a[k], lb = dec_b[k], ls = dec_skip[k], ll = dec_low[k];
-    // second conv of the DoubleConvolution (k == 2: dy already produced by the fused tail above)
-    if (k != 2) SIFSR_TRY(bn_unit_bwd(c, lb, c.f(w.g[lb]), grads, nullptr, up_rows, 0));
+    // second conv of the DoubleConvolution (k == 2: dy already produced by the fused tail above, or formed from dsr while staging)
+    if (k != 2) SIFSR_TRY(bn_unit_bwd(c, lb, nullptr, up_rows, 0));
     int rows_a = 0;
-    bool fused_b = false;
-    SIFSR_TRY(conv_unit_bwd16(c, lb, src_act(c, la), k == 2 && tail_in_bwd16 ? dsr : c.f(w.g[lb]), c.f(w.g[la]), nullptr, la, &rows_a,
-                              k == 2 ? (tail_in_bwd16 ? 2 : 0) : 1, &fused_b));
-    if (fused_b) last_fused = lb;
-    if (!fused_b) {
-      SIFSR_TRY(conv_unit_wgrad(c, lb, src_act(c, la), src_none(), c.f(w.g[lb]), grads, k == 2));
-      SIFSR_TRY(conv_unit_dgrad(c, lb, c.f(w.g[lb]), c.f(w.g[la]), nt.L[la].cout, nt.L[lb].cin, nullptr, 0, nullptr, la, &rows_a, k == 2));
-    }
+    SIFSR_TRY(conv_unit_bwd(c, lb, src_act(c, la), k == 2 && tail_in_bwd16 ? dsr : c.g(lb), c.g(la), nullptr, la, &rows_a,
+                            k == 2 ? (tail_in_bwd16 ? 2 : 0) : 1));
     // first conv: input = cat([U_k, relu(bn(y_skip))])
-    SIFSR_TRY(bn_unit_bwd(c, la, c.f(w.g[la]), grads, nullptr, rows_a));
-    SIFSR_TRY(conv_unit_wgrad(c, la, src_raw(c.f(w.U[k]), uc[k]), src_act(c, ls), c.f(w.g[la]), grads));
-    SIFSR_TRY(conv_unit_dgrad(c, la, c.f(w.g[la]), c.f(w.gU[k]), uc[k], uc[k], c.f(w.g[ls]), nt.L[ls].cout, nullptr));
+    SIFSR_TRY(bn_unit_bwd(c, la, nullptr, rows_a));
+    SIFSR_TRY(conv_unit_wgrad(c, la, src_raw(c.f(w.U[k]), uc[k]), src_act(c, ls), c.g(la)));
+    SIFSR_TRY(conv_unit_dgrad(c, la, c.g(la), c.f(w.gU[k]), uc[k], uc[k], c.g(ls), nt.L[ls].cout, nullptr));
     up_rows = up2x_bwd_stat_rows(B, c.lvH(lv + 1), c.lvW(lv + 1), uc[k]);
     if ((size_t)up_rows * uc[k] * 2 > w.partials_cap) up_rows = 0;
-    SIFSR_TRY(launch_up2x_bwd(c.f(w.gU[k]), c.f(w.g[ll]), B, c.lvH(lv + 1), c.lvW(lv + 1), uc[k], s,
-                              up_rows ? c.f(w.y[ll]) : nullptr, up_rows ? c.scale(ll) : nullptr, up_rows ? c.shift(ll) : nullptr,
+    SIFSR_TRY(launch_up2x_bwd(c.f(w.gU[k]), c.g(ll), B, c.lvH(lv + 1), c.lvW(lv + 1), uc[k], s,
+                              up_rows ? c.y(ll) : nullptr, up_rows ? c.scale(ll) : nullptr, up_rows ? c.shift(ll) : nullptr,
                               up_rows ? c.f(w.partials) : nullptr));
   }
 
   // encoder, last to first
-  static const int enc_prev[3] = {L_IN3, L_D1C, L_D2C};
-  static const int enc_a[3] = {L_D1A, L_D2A, L_D3A}, enc_b[3] = {L_D1B, L_D2B, L_D3B}, enc_c[3] = {L_D1C, L_D2C, L_D3C};
-  static const int pc[3] = {16, 32, 64};
-  static const int early_reduce = getenv("SIFSR_DBG_EARLY_REDUCE") ? atoi(getenv("SIFSR_DBG_EARLY_REDUCE")) : 3;   // 0: one batch at the end; 1: + one before db1; 2: + one after the decoder; 3: one per encoder stage
   for (int k = 2; k >= 0; --k) {
-    const int la = enc_a[k], lb = enc_b[k], lc = enc_c[k], lp = enc_prev[k];
-    if (c.side != nullptr && (early_reduce == 1 ? k == 0 : early_reduce == 2 ? (k == 0 || k == 2) : early_reduce == 3 ? true : false)) {
-      // the slabs of every layer so far are reduced NOW on the second stream, between its weight gradients (one batch per encoder
-      // stage), instead of in one batch at the end: there the whole reduction -- 370 MB then, HBM-bound -- ran beside the first
-      // layer's weight gradient, the last kernel of the chain and HBM-bound like it, and set the end of the step
-      if (last_fused >= 0) {
-        if (hipStreamWaitEvent(c.side->s, c.side->ev[last_fused], 0) != hipSuccess) return SIFSR_ERR_ARG;
-        lane_guard.forked = true;
-      }
-      SIFSR_TRY(finish_wgrads(c.side->s));
-      njobs = 0;
-    }
+    const int la = enc_a[k], lb = enc_b[k], lc = enc_c[k];
+    // SIFSR_DBG_EARLY_REDUCE (switches.h): the slabs of every layer so far are reduced NOW on the second stream, between its weight
+    // gradients (3: one batch per encoder stage), instead of in one batch at the end: there the whole reduction -- 370 MB then,
+    // HBM-bound -- ran beside the first layer's weight gradient, the last kernel of the chain and HBM-bound like it, and set the
+    // end of the step
+    const int er = sw.early_reduce;
+    if (c.side != nullptr && (er == 3 || (er == 2 && k != 1) || (er == 1 && k == 0))) SIFSR_TRY(finish_wgrads_side(c));
     // lastconv: input R_k = P_k + relu(bn(y_b)); its gradient is both g(a_b) and part of g(P_k).
     // y_c also feeds the next pooling stage (k < 2): that AvgPool adjoint (of gP[k+1], computed in the previous
     // iteration) is folded into this BatchNorm backward instead of a separate accumulate pass over g[lc].
     // (k == 2: g of db3.lastconv came from the last upsample adjoint above, with its sums)
-    SIFSR_TRY(bn_unit_bwd(c, lc, c.f(w.g[lc]), grads, k < 2 ? c.f(w.gP[k + 1]) : nullptr, k == 2 ? up_rows : 0, 0));
-    SIFSR_TRY(conv_unit_wgrad(c, lc, src_raw(c.f(w.R[k]), pc[k]), src_none(), c.f(w.g[lc]), grads));
+    SIFSR_TRY(bn_unit_bwd(c, lc, k < 2 ? c.f(w.gP[k + 1]) : nullptr, k == 2 ? up_rows : 0, 0));
+    SIFSR_TRY(conv_unit_wgrad(c, lc, src_raw(c.f(w.R[k]), pc[k]), src_none(), c.g(lc)));
     int rows_b = 0, rows_a = 0;
-    SIFSR_TRY(conv_unit_dgrad(c, lc, c.f(w.g[lc]), c.f(w.g[lb]), pc[k], pc[k], nullptr, 0, nullptr, lb, &rows_b));
+    SIFSR_TRY(conv_unit_dgrad(c, lc, c.g(lc), c.g(lb), pc[k], pc[k], nullptr, 0, nullptr, lb, &rows_b));
     // residual DoubleConvolution (g[lb] survives untouched: it is also the skip gradient added to gP[k] below)
-    SIFSR_TRY(bn_unit_bwd(c, lb, c.f(w.g[lb]), grads, nullptr, rows_b));
-    bool fused_b = false;
-    SIFSR_TRY(conv_unit_bwd16(c, lb, src_act(c, la), c.f(w.g[lb]), c.f(w.g[la]), nullptr, la, &rows_a, 1, &fused_b));
-    if (fused_b) last_fused = lb;
-    if (!fused_b) {
-      SIFSR_TRY(conv_unit_wgrad(c, lb, src_act(c, la), src_none(), c.f(w.g[lb]), grads));
-      SIFSR_TRY(conv_unit_dgrad(c, lb, c.f(w.g[lb]), c.f(w.g[la]), pc[k], pc[k], nullptr, 0, nullptr, la, &rows_a));
-    }
-    SIFSR_TRY(bn_unit_bwd(c, la, c.f(w.g[la]), grads, nullptr, rows_a));
-    bool fused_a = false;
-    SIFSR_TRY(conv_unit_bwd16(c, la, src_raw(c.f(w.P[k]), pc[k]), c.f(w.g[la]), c.f(w.gP[k]), c.f(w.g[lb]), -1, nullptr, 1, &fused_a));
-    if (fused_a) last_fused = la;
-    if (!fused_a) {
-      SIFSR_TRY(conv_unit_wgrad(c, la, src_raw(c.f(w.P[k]), pc[k]), src_none(), c.f(w.g[la]), grads));
-      SIFSR_TRY(conv_unit_dgrad(c, la, c.f(w.g[la]), c.f(w.gP[k]), pc[k], pc[k], nullptr, 0, c.f(w.g[lb])));
-    }
-    // AvgPool adjoint of gP[k] onto the skip gradient g[lp]: folded into the BatchNorm backward of lp (above / below)
-    (void)lp;
+    SIFSR_TRY(bn_unit_bwd(c, lb, nullptr, rows_b));
+    SIFSR_TRY(conv_unit_bwd(c, lb, src_act(c, la), c.g(lb), c.g(la), nullptr, la, &rows_a));
+    SIFSR_TRY(bn_unit_bwd(c, la, nullptr, rows_a));
+    SIFSR_TRY(conv_unit_bwd(c, la, src_raw(c.f(w.P[k]), pc[k]), c.g(la), c.f(w.gP[k]), c.g(lb), -1, nullptr));
+    // AvgPool adjoint of gP[k] onto the skip gradient g[enc_prev[k]]: folded into the BatchNorm backward of that layer (above / below)
   }
 
   // inbloc
   // inbloc.bloc.3 also feeds the first pooling stage: its gradient is g (the decoder skip) + the AvgPool adjoint of gP[0].  Where the
   // fused kernel runs it adds the adjoint while staging (a 67 MB read) and the reduction does not write the sum back (268 MB)
-  static const int pool_on_load_env = getenv("SIFSR_DBG_POOL_ON_LOAD") ? atoi(getenv("SIFSR_DBG_POOL_ON_LOAD")) : 1;
-  const bool pool_on_load = pool_on_load_env != 0 && bwd16_usable(c, L_IN3, src_act(c, L_IN0));
-  SIFSR_TRY(bn_unit_bwd(c, L_IN3, c.f(w.g[L_IN3]), grads, c.f(w.gP[0]), 0, -1, !pool_on_load));
+  const bool pool_on_load = sw.pool_on_load != 0 && bwd16_usable(c, L_IN3, src_act(c, L_IN0));
+  SIFSR_TRY(bn_unit_bwd(c, L_IN3, c.f(w.gP[0]), 0, -1, !pool_on_load));
   int rows_in0 = 0;
   bool fused_in3 = false;
-  SIFSR_TRY(conv_unit_bwd16(c, L_IN3, src_act(c, L_IN0), c.f(w.g[L_IN3]), c.f(w.g[L_IN0]), nullptr, L_IN0, &rows_in0, 1, &fused_in3, head_linear,
+  SIFSR_TRY(conv_unit_bwd16(c, L_IN3, src_act(c, L_IN0), c.g(L_IN3), c.g(L_IN0), nullptr, L_IN0, &rows_in0, 1, &fused_in3, head_linear,
                             pool_on_load ? c.f(w.gP[0]) : nullptr));
   if (pool_on_load && !fused_in3) return SIFSR_ERR_ARG;
   if (head_linear && !fused_in3) return SIFSR_ERR_ARG;
-  if (fused_in3) last_fused = L_IN3;
-  if (!fused_in3) SIFSR_TRY(conv_unit_wgrad(c, L_IN3, src_act(c, L_IN0), src_none(), c.f(w.g[L_IN3]), grads));
-  // that was the last MFMA layer: all 16 layers' weight-gradient slabs -> OIHW gradients, one launch.  With the second
-  // stream it follows the last weight gradient there (it writes only the conv-weight regions of `grads`, which nothing
-  // on the caller's stream touches) and overlaps the head of the chain instead of trailing it.  The fused 16 -> 16 kernels
-  // wrote their slabs on the CALLER's stream: the last of them (ev[] recorded in enqueue order, so it covers every earlier
-  // one) is what the second stream waits for.
-  if (c.side != nullptr) {
-    if (last_fused >= 0) {
-      if (hipStreamWaitEvent(c.side->s, c.side->ev[last_fused], 0) != hipSuccess) return SIFSR_ERR_ARG;
-      lane_guard.forked = true;
-    }
-    SIFSR_TRY(finish_wgrads(c.side->s));
-  }
-  if (!fused_in3) SIFSR_TRY(conv_unit_dgrad(c, L_IN3, c.f(w.g[L_IN3]), c.f(w.g[L_IN0]), 16, 16, nullptr, 0, nullptr, L_IN0, &rows_in0));
+  // (not conv_unit_bwd: without the fused kernel the slab reduction below goes BETWEEN the weight and the input gradient)
+  if (!fused_in3) SIFSR_TRY(conv_unit_wgrad(c, L_IN3, src_act(c, L_IN0), src_none(), c.g(L_IN3)));
+  // that was the last MFMA layer: all 16 layers' weight-gradient slabs -> OIHW gradients.  With the second stream the reduction
+  // follows the last weight gradient there and overlaps the head of the chain instead of trailing it.
+  if (c.side != nullptr) SIFSR_TRY(finish_wgrads_side(c));
+  if (!fused_in3) SIFSR_TRY(conv_unit_dgrad(c, L_IN3, c.g(L_IN3), c.g(L_IN0), 16, 16, nullptr, 0, nullptr, L_IN0, &rows_in0));
   // first layer: no input gradient, so dy(L_IN0) is consumed by the weight gradient alone and is formed on the
   // fly from (g, y) in its staging loop; its BatchNorm-backward sums came out of the dgrad above -> finalize only
   {
     const LayerInfo& L = nt.L[L_IN0];
-    const size_t npix = w.npix[0];
-    const float* y = c.f(w.y[L_IN0]);
     if (rows_in0 > 0) {
-      SIFSR_TRY(bn_unit_bwd(c, L_IN0, c.f(w.g[L_IN0]), grads, nullptr, rows_in0));
+      SIFSR_TRY(bn_unit_bwd(c, L_IN0, nullptr, rows_in0));
     } else {
-      const size_t nb = npix / 256;
-      const int nblk_r = (int)(nb > 1024 ? 1024 : (nb < 1 ? 1 : nb));
-      SIFSR_TRY(launch_bn_bwd_reduce(c.f(w.g[L_IN0]), y, c.scale(L_IN0), c.shift(L_IN0), c.f(w.mean) + L.ch_off,
-                                     c.f(w.invstd) + L.ch_off, 16, npix, c.f(w.partials), nblk_r, s));
-      SIFSR_TRY(launch_bn_bwd_finalize(c.f(w.partials), nblk_r, 16, (double)npix, c.scale(L_IN0), c.f(w.mean) + L.ch_off,
-                                       c.f(w.invstd) + L.ch_off, grads + L.gamma_off, grads + L.beta_off,
-                                       reinterpret_cast<double*>(c.f(w.coef)), s));
+      // (not bn_unit_bwd: this finalize is launched WITHOUT the shift / beta / coef_f arguments -- the first layer's consumer reads
+      // the float64 coefficients only -- so folding it in would change what is written)
+      const size_t npix = w.npix[0];
+      const int nblk_r = bn_bwd_reduce_blocks(npix);
+      SIFSR_TRY(launch_bn_bwd_reduce(c.g(L_IN0), c.y(L_IN0), c.scale(L_IN0), c.shift(L_IN0), c.mean(L_IN0), c.invstd(L_IN0), 16, npix,
+                                     c.f(w.partials), nblk_r, s));
+      SIFSR_TRY(launch_bn_bwd_finalize(c.f(w.partials), nblk_r, 16, (double)npix, c.scale(L_IN0), c.mean(L_IN0), c.invstd(L_IN0),
+                                       grads + L.gamma_off, grads + L.beta_off, c.coef(), s));
     }
     int nblk = B * ((H + 15) / 16) * ((W + 15) / 16);
     if (head_linear) {      // g[L_IN0] holds dz
       if (nblk > 768) nblk = 768;
-      SIFSR_TRY(launch_conv_in_dz_wgrad(x, c.f(w.g[L_IN0]), c.f(w.slabs), nblk, B, H, W, s));
+      SIFSR_TRY(launch_conv_in_dz_wgrad(x, c.g(L_IN0), c.f(w.slabs), nblk, B, H, W, s));
       if (c.side != nullptr && hipStreamWaitEvent(s, c.side->aux, 0) != hipSuccess) return SIFSR_ERR_ARG;
-      SIFSR_TRY(launch_conv_in_dw_combine(c.f(w.slabs), nblk, conv_in_gram_result(c.f(w.gram)), params + L.w_off,
-                                          reinterpret_cast<const double*>(c.f(w.coef)), grads + L.w_off, s));
+      SIFSR_TRY(launch_conv_in_dw_combine(c.f(w.slabs), nblk, conv_in_gram_result(c.f(w.gram)), params + L.w_off, c.coef(),
+                                          grads + L.w_off, s));
     } else {
       if (nblk > 1024) nblk = 1024;
-      SIFSR_TRY(launch_conv_in_wgrad_fused(x, c.f(w.g[L_IN0]), y, c.scale(L_IN0), c.shift(L_IN0),
-                                           reinterpret_cast<const double*>(c.f(w.coef)), c.f(w.slabs), nblk,
+      SIFSR_TRY(launch_conv_in_wgrad_fused(x, c.g(L_IN0), c.y(L_IN0), c.scale(L_IN0), c.shift(L_IN0), c.coef(), c.f(w.slabs), nblk,
                                            grads + L.w_off, B, H, W, s));
     }
   }
   if (c.side != nullptr) {   // hand the second stream's work back to the caller's stream
     SIFSR_TRY(lane_guard.join());
   } else {
-    SIFSR_TRY(finish_wgrads(s));
+    SIFSR_TRY(finish_wgrads(c, s));
   }
   return SIFSR_OK;
 }

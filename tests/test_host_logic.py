@@ -300,22 +300,64 @@ print(_lib.call("sifsr_model_workspace_bytes", 64, 256, 256, 1))
 
 
 def test_bwd16_grid_knob_below_one_falls_back_to_the_default():
-    """SIFSR_DBG_BWD16_GRID sizes the fused 16 -> 16 backward's persistent grid, and the workspace layout asks for that grid
-    (conv3x3_bwd16_grid divides by the knob).  0 used to kill the process with SIGFPE and a negative value gave a launch of grid 0:
-    values below 1 fall back to the default, so the workspace of the bench shape must be the one without the knob.  The knob is
-    read once per process, so each value runs in a child of its own."""
-    import subprocess
-
-    def workspace_bytes(knob):
-        env = {k: v for k, v in os.environ.items() if k != "SIFSR_DBG_BWD16_GRID"}
-        env["SIFSR_ROOT"] = ROOT
-        if knob is not None:
-            env["SIFSR_DBG_BWD16_GRID"] = knob
-        r = subprocess.run([sys.executable, "-c", GRID_WORKER], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, (knob, r.returncode, r.stdout[-2000:] + r.stderr[-3000:])
-        return int(r.stdout.strip().splitlines()[-1])
-
-    ref = workspace_bytes(None)
+    """SIFSR_DBG_BWD16_GRID used to size the fused 16 -> 16 backward's persistent grid (conv3x3_bwd16_grid divided by it: 0 killed the
+    process with SIGFPE, a negative value gave a launch of grid 0, so values below 1 fell back to the default).  The knob is removed:
+    the grid is the constant 256 and the variable is ignored, so the workspace of the bench shape is the default one whatever it
+    holds.  Each value runs in a child of its own, as when the knob was read once per process."""
+    ref = _workspace_bytes_in_child("SIFSR_DBG_BWD16_GRID", None)
     assert ref > 0
     for knob in ("0", "-5"):
-        assert workspace_bytes(knob) == ref, knob
+        assert _workspace_bytes_in_child("SIFSR_DBG_BWD16_GRID", knob) == ref, knob
+
+
+def _workspace_bytes_in_child(var, value):
+    """sifsr_model_workspace_bytes of the bench shape (64, 256, 256, training) in a child process with `var` = value (None: unset)."""
+    import subprocess
+
+    env = {k: v for k, v in os.environ.items() if k != var}
+    env["SIFSR_ROOT"] = ROOT
+    if value is not None:
+        env[var] = value
+    r = subprocess.run([sys.executable, "-c", GRID_WORKER], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (var, value, r.returncode, r.stdout[-2000:] + r.stderr[-3000:])
+    return int(r.stdout.strip().splitlines()[-1])
+
+
+def test_switch_parser_takes_any_value_and_the_workspace_covers_both_wgrad_families():
+    """The one switch parser (csrc/switches.h): unset -> default, otherwise atoi.  SIFSR_WGRAD_WINO chooses between the tap-domain and
+    the Winograd-domain weight-gradient kernels (1 / 2: Winograd, anything else: tap domain); the slab regions are sized for both
+    families, so every value -- listed, out of range, negative, unparsable -- leaves the process alive and the workspace unchanged.
+    The switches are read once per process, so each value runs in a child of its own."""
+    ref = _workspace_bytes_in_child("SIFSR_WGRAD_WINO", None)
+    assert ref > 0
+    for value in ("0", "1", "2", "7", "-1", "x"):
+        assert _workspace_bytes_in_child("SIFSR_WGRAD_WINO", value) == ref, value
+
+
+REMOVED_KNOBS = ("SIFSR_DBG_CONV_GRID", "SIFSR_DBG_BWD16_GRID", "SIFSR_DBG_WGRAD_GRID_PCT", "SIFSR_DBG_WGRAD_WINO_GRID",
+                 "SIFSR_DBG_WGRAD_WINO_GRID11", "SIFSR_DBG_WGRAD_WINO_GRID42", "SIFSR_DBG_WGRAD_WINO_SPLIT64", "SIFSR_DBG_WINO8_DEPTH",
+                 "SIFSR_NO_WINO_WGRAD")
+
+
+def test_environment_is_read_in_one_place_and_documented():
+    """The library reads its run-time switches in ONE file under csrc/ (the identifier getenv occurs nowhere else), every switch name
+    that file's parsing code holds as a string literal is listed in INTEGRATION.md, and the removed tuning knobs are named neither in
+    csrc/ nor in INTEGRATION.md."""
+    import glob
+    import re
+
+    pkg = os.path.join(ROOT, "land-surface-temperature-super-resolution-with-a-scale-invariance-free-neural-approach_amd")
+    files = sorted(glob.glob(os.path.join(pkg, "csrc", "*")))
+    assert len(files) > 20
+    texts = {f: open(f).read() for f in files}
+    readers = [f for f, t in texts.items() if re.search(r"\bgetenv\b", t)]
+    assert len(readers) == 1, readers
+    names = set(re.findall(r'"(SIFSR_[A-Z0-9_]+)"', texts[readers[0]]))
+    assert len(names) == 10, sorted(names)
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    documented = set(re.findall(r"SIFSR_[A-Z0-9_]+", doc))
+    assert names <= documented, sorted(names - documented)
+    # whole names: SIFSR_DBG_WGRAD_WINO_GRID is a prefix of two others
+    for f, t in list(texts.items()) + [("INTEGRATION.md", doc)]:
+        found = set(re.findall(r"SIFSR_[A-Z0-9_]+", t)) & set(REMOVED_KNOBS)
+        assert not found, (f, sorted(found))
