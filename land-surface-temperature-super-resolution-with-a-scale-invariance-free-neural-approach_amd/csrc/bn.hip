@@ -228,7 +228,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_finalize2_kernel(const float* __res
   }
 }
 
-template <int C>
+template <int C, bool HS>   // HS: g, y, gp and dy stored as bf16, like the reduction above
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ g, const float* __restrict__ y,
                                                            const float* __restrict__ scale,
                                                            const float* __restrict__ shift,
@@ -242,15 +242,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
 #pragma unroll
   for (int j = 0; j < 4; ++j) { sd[j] = coef[4 * c4 + j]; k1[j] = coef[C + 4 * c4 + j]; k0[j] = coef[2 * C + 4 * c4 + j]; }
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < nquads; e += (size_t)gridDim.x * 256) {
-    const float4 yv = ld4(y + e * 4);
-    float4 gv = ld4(g + e * 4);
-    if (pa.gp != nullptr) { const float4 q = pool_adj4<C>(pa, e / Q, c4); gv.x += q.x; gv.y += q.y; gv.z += q.z; gv.w += q.w; }
+    const float4 yv = ldA4<HS>(y, e * 4);
+    float4 gv = ldA4<HS>(g, e * 4);
+    if (pa.gp != nullptr) { const float4 q = pool_adj4<C, HS>(pa, e / Q, c4); gv.x += q.x; gv.y += q.y; gv.z += q.z; gv.w += q.w; }
     float4 o;
     o.x = (float)fma(sd[0], (double)(fmaf(yv.x, sc.x, sh.x) > 0.f ? gv.x : 0.f), fma(k1[0], (double)yv.x, k0[0]));
     o.y = (float)fma(sd[1], (double)(fmaf(yv.y, sc.y, sh.y) > 0.f ? gv.y : 0.f), fma(k1[1], (double)yv.y, k0[1]));
     o.z = (float)fma(sd[2], (double)(fmaf(yv.z, sc.z, sh.z) > 0.f ? gv.z : 0.f), fma(k1[2], (double)yv.z, k0[2]));
     o.w = (float)fma(sd[3], (double)(fmaf(yv.w, sc.w, sh.w) > 0.f ? gv.w : 0.f), fma(k1[3], (double)yv.w, k0[3]));
-    st4(dy + e * 4, o);
+    stA4<HS>(dy, e * 4, o);
   }
 }
 
@@ -342,12 +342,16 @@ int launch_bn_bwd_apply(const float* g, const float* y, const float* scale, cons
   const size_t nquads = npix * (size_t)C / 4;
   size_t blocks = (nquads + 255) / 256;
   if (blocks > 8192) blocks = 8192;
+  // the activation tensors follow the calling thread's storage mode (sifsr_set_op_storage_bf16), as in the reduction
+  const bool hs = sifsr_half_storage();
+#define BN_APPLY(C_, HS_) hipLaunchKernelGGL((bn_bwd_apply_kernel<C_, HS_>), dim3((int)blocks), dim3(256), 0, s, g, y, scale, shift, coef, nquads, dy, pa)
   switch (C) {
-    case 16: hipLaunchKernelGGL((bn_bwd_apply_kernel<16>), dim3((int)blocks), dim3(256), 0, s, g, y, scale, shift, coef, nquads, dy, pa); break;
-    case 32: hipLaunchKernelGGL((bn_bwd_apply_kernel<32>), dim3((int)blocks), dim3(256), 0, s, g, y, scale, shift, coef, nquads, dy, pa); break;
-    case 64: hipLaunchKernelGGL((bn_bwd_apply_kernel<64>), dim3((int)blocks), dim3(256), 0, s, g, y, scale, shift, coef, nquads, dy, pa); break;
+    case 16: if (hs) BN_APPLY(16, true); else BN_APPLY(16, false); break;
+    case 32: if (hs) BN_APPLY(32, true); else BN_APPLY(32, false); break;
+    case 64: if (hs) BN_APPLY(64, true); else BN_APPLY(64, false); break;
     default: return SIFSR_ERR_SHAPE;
   }
+#undef BN_APPLY
   SIFSR_LAUNCH_CHECK();
   return SIFSR_OK;
 }

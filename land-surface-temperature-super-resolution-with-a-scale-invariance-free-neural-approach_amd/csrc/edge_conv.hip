@@ -237,6 +237,7 @@ __global__ __launch_bounds__(256) void conv_out_fwd_kernel(const float* __restri
 }
 
 // output conv input-gradient: g[q][ci] = sum_t w[ci][t] * sum_{p: clamp(p+t)=q} dsr[p]  (replicate adjoint)
+template <bool HS>   // HS: g stored as bf16 (dsr and w stay fp32 in every mode)
 __global__ __launch_bounds__(256) void conv_out_dgrad_kernel(const float* __restrict__ dsr, const float* __restrict__ w,
                                                              float* __restrict__ g, int B, int H, int W) {
   const size_t n = (size_t)B * H * W;
@@ -257,7 +258,6 @@ __global__ __launch_bounds__(256) void conv_out_dgrad_kernel(const float* __rest
         for (int ix = 0; ix < nx; ++ix) s += dsr[img + (size_t)ys[iy] * W + xs[ix]];
       S[t] = s;
     }
-    float* gp = g + q * 16;
 #pragma unroll
     for (int c4 = 0; c4 < 4; ++c4) {
       float o[4];
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(256) void conv_out_dgrad_kernel(const float* __rest
         for (int t = 0; t < 9; ++t) s = fmaf(w[(4 * c4 + j) * 9 + t], S[t], s);
         o[j] = s;
       }
-      st4(gp + 4 * c4, make_float4(o[0], o[1], o[2], o[3]));
+      stA4<HS>(g, q * 16 + 4 * c4, make_float4(o[0], o[1], o[2], o[3]));
     }
   }
 }
@@ -278,6 +278,7 @@ __global__ __launch_bounds__(256) void conv_out_dgrad_kernel(const float* __rest
 // on the tap:  D[ci][t] = sum_{p'} a[p'][ci] * dsr[p' - t]   (dsr = 0 outside the 16x16 tile).
 //   A lane (i = ci, k = pixel) <- a halo tile [18 rows][20 cols (2 zero pad)][OCS]
 //   B lane (j = t,  k = pixel) <- dsr tile at the per-lane tap shift
+template <bool HS>   // HS: y stored as bf16
 __global__ __launch_bounds__(256) void conv_out_wgrad_kernel(const float* __restrict__ y, const float* scale,
                                                              const float* shift, const float* __restrict__ dsr,
                                                              float* __restrict__ partials, int B, int H, int W) {
@@ -300,7 +301,7 @@ __global__ __launch_bounds__(256) void conv_out_wgrad_kernel(const float* __rest
       const int p = e >> 2, c4 = e & 3;
       const int py = p / 18, px = p - py * 18;
       const int gy = clampi(y0 - 1 + py, 0, H - 1), gx = clampi(x0 - 1 + px, 0, W - 1);
-      float4 v = ld4(y + ((size_t)(b * H + gy) * W + gx) * 16 + 4 * c4);
+      float4 v = ldA4<HS>(y, ((size_t)(b * H + gy) * W + gx) * 16 + 4 * c4);
       if (scale != nullptr) v = bn_relu4(v, ld4(scale + 4 * c4), ld4(shift + 4 * c4));
       *reinterpret_cast<float4*>(&tile[(py * 20 + px) * OCS + 4 * c4]) = v;
     }
@@ -667,7 +668,8 @@ int launch_conv_out_dgrad(const float* dsr, const float* w, float* g, int B, int
   const size_t n = (size_t)B * H * W;
   int blocks = (int)((n + 255) / 256);
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(conv_out_dgrad_kernel, dim3(blocks), dim3(256), 0, s, dsr, w, g, B, H, W);
+  if (sifsr_half_storage()) hipLaunchKernelGGL(conv_out_dgrad_kernel<true>, dim3(blocks), dim3(256), 0, s, dsr, w, g, B, H, W);
+  else hipLaunchKernelGGL(conv_out_dgrad_kernel<false>, dim3(blocks), dim3(256), 0, s, dsr, w, g, B, H, W);
   SIFSR_LAUNCH_CHECK();
   return SIFSR_OK;
 }
@@ -675,7 +677,8 @@ int launch_conv_out_dgrad(const float* dsr, const float* w, float* g, int B, int
 int launch_conv_out_wgrad(const float* y, const float* scale, const float* shift, const float* dsr, float* partials,
                           int nblk, float* dw, float* db, int B, int H, int W, hipStream_t s) {
   if (H < 1 || W < 1) return SIFSR_ERR_SHAPE;
-  hipLaunchKernelGGL(conv_out_wgrad_kernel, dim3(nblk), dim3(256), 0, s, y, scale, shift, dsr, partials, B, H, W);
+  if (sifsr_half_storage()) hipLaunchKernelGGL(conv_out_wgrad_kernel<true>, dim3(nblk), dim3(256), 0, s, y, scale, shift, dsr, partials, B, H, W);
+  else hipLaunchKernelGGL(conv_out_wgrad_kernel<false>, dim3(nblk), dim3(256), 0, s, y, scale, shift, dsr, partials, B, H, W);
   // dw (144 floats) and db (1 float) are adjacent in the flat gradient buffer (outlay.weight, outlay.bias)
   if (db != dw + 144) return SIFSR_ERR_ARG;
   hipLaunchKernelGGL(sum_partials_kernel, dim3(37), dim3(256), 0, s, partials, nblk, 145, dw);
