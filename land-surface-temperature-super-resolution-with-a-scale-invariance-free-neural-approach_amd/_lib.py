@@ -2,7 +2,8 @@
 
 The signatures are parsed from ``include/sifsr_hip.h`` -- the header is the single source of truth
 for the C ABI, and ``tests/test_capi_symbols.py`` checks that the library exports every declared
-symbol.  There is NO fallback: if the library is missing or a call fails, we raise.
+symbol -- and from its extension ``include/sifsr_mosaic.h`` (prefix ``sifsrx_``, same declaration style,
+gated by ``tests/test_mosaic_host.py``).  There is NO fallback: if the library is missing or a call fails, we raise.
 """
 from __future__ import annotations
 
@@ -15,6 +16,7 @@ import torch  # noqa: F401  (must be imported first: the library binds to the li
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 HEADER = os.path.join(_ROOT, "include", "sifsr_hip.h")
+EXTENSION_HEADER = os.path.join(_ROOT, "include", "sifsr_mosaic.h")
 # SIFSR_LIB: another build of the same C ABI (same-device A/B of kernel variants, tools/ab/); default: the in-tree library
 LIB_PATH = os.environ.get("SIFSR_LIB") or os.path.join(_HERE, "libsifsr_hip.so")
 
@@ -61,7 +63,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        _decls = parse_header()
+        _decls = {**parse_header(), **parse_header(EXTENSION_HEADER)}
         for name, (ret, args) in _decls.items():
             fn = getattr(handle, name)     # AttributeError if the library lacks a declared symbol
             fn.restype = ret
@@ -72,6 +74,11 @@ def lib():
 
 def declared_symbols():
     return sorted(parse_header().keys())
+
+
+def declared_extension_symbols():
+    """The names ``include/sifsr_mosaic.h`` declares (``sifsrx_*``); ``declared_symbols`` stays the main header's."""
+    return sorted(parse_header(EXTENSION_HEADER).keys())
 
 
 def _conv(v):
@@ -86,7 +93,7 @@ def call(name: str, *args):
     """Call a C-ABI function; tensors are passed as device pointers.  Raises on a non-zero status."""
     fn = getattr(lib(), name)
     rc = fn(*[_conv(a) for a in args])
-    if fn.restype is ctypes.c_int and rc != 0 and not name.startswith(("sifsr_abi", "sifsr_num", "sifsr_layer", "sifsr_huber_partial", "sifsr_model_workspace_regions", "sifsr_conv3x3_stat", "sifsr_conv_in_stat", "sifsr_conv3x3_bwd16_stat", "sifsr_profile_add", "sifsr_up2x_bwd_stat")):
+    if fn.restype is ctypes.c_int and rc != 0 and not name.startswith(("sifsr_abi", "sifsr_num", "sifsr_layer", "sifsr_huber_partial", "sifsr_model_workspace_regions", "sifsr_conv3x3_stat", "sifsr_conv_in_stat", "sifsr_conv3x3_bwd16_stat", "sifsr_profile_add", "sifsr_up2x_bwd_stat", "sifsrx_tile_")):
         raise SifsrError(f"{name} failed with status {rc}")
     return rc
 

@@ -33,7 +33,8 @@ def build(force=False, verbose=False, extra=(), lib=None, obj_dir=None, csrc=Non
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdrs.append(os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "sifsr_hip.h"))
+    inc = os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include")
+    hdrs += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")]      # sifsr_hip.h and its extension sifsr_mosaic.h
     os.makedirs(OBJ_, exist_ok=True)
     jobs = []
     for f in srcs:

@@ -10,18 +10,9 @@
 //    window, sample covariance, K1 = 0.01, K2 = 0.03, data_range = max - min of the TARGET BATCH, mean over
 //    the window-valid interior), batch means as two device scalars -- no D2H of the images, no host stall.
 #include "edge_conv.h"
+#include "mosaic.h"   // tile_prepare_rows: the per-tile body shared with the overlapped layout
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------
-// bicubic x4 (ATen upsample_bicubic2d / OpenCV INTER_CUBIC coefficients, A = -0.75)
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float cc1(float x, float A) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; }
-__device__ __forceinline__ float cc2(float x, float A) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; }
-__device__ __forceinline__ void cubic_coeffs(float t, float c[4]) {
-  const float A = -0.75f;
-  c[0] = cc2(t + 1.f, A); c[1] = cc1(t, A); c[2] = cc1(1.f - t, A); c[3] = cc2(2.f - t, A);
-}
 
 struct TileGeom {
   int tiles_x;                        // tile t -> (ty, tx) = (t / tiles_x, t % tiles_x)
@@ -31,61 +22,18 @@ struct TileGeom {
   int ndvi_row;
 };
 
-// one workgroup = 16 output rows x (4*win) columns of one tile; thread = output column (win = 64 -> 256 threads)
+// one workgroup = 16 output rows x (4*win) columns of one tile; thread = output column (win = 64 -> 256 threads); body: mosaic.h
 __global__ __launch_bounds__(256) void tiles_prepare_kernel(const float* __restrict__ lst, const float* __restrict__ ndvi,
                                                             float* __restrict__ x, const TileGeom gm, int win,
                                                             float mean_lst, float istd_lst, float mean_ndvi,
                                                             float istd_ndvi, int clip_ndvi) {
   __shared__ float src[8][64 + 1];
   const int hr = 4 * win;
-  const int t = blockIdx.x, Y0 = blockIdx.y * 16, X = threadIdx.x;
+  const int t = blockIdx.x;
   const int ty = t / gm.tiles_x, tx = t - ty * gm.tiles_x;
-  const float* lt = lst + ty * gm.lst_step_y + tx * gm.lst_step_x;
-  const float* nt = ndvi + ty * gm.ndvi_step_y + tx * gm.ndvi_step_x;
-  const int sy0 = Y0 / 4 - 2;   // first of the 8 source rows the 16 output rows touch
-  for (int e = threadIdx.x; e < 8 * win; e += 256) {
-    const int r = e / win, cidx = e - r * win;
-    const int gy = clampi(sy0 + r, 0, win - 1);
-    src[r][cidx] = (lt[(size_t)gy * gm.lst_row + cidx] - mean_lst) * istd_lst;
-  }
-  __syncthreads();
-  float* o0 = x + ((size_t)t * 2 + 0) * hr * hr;
-  float* o1 = x + ((size_t)t * 2 + 1) * hr * hr;
-  if (X < hr) {
-    // horizontal pass: source index of output column X (scale 1/4, half-pixel centres)
-    const float sx = 0.25f * ((float)X + 0.5f) - 0.5f;
-    const float fx = floorf(sx);
-    const int ix = (int)fx;
-    float cx[4];
-    cubic_coeffs(sx - fx, cx);
-    int xs[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) xs[j] = clampi(ix - 1 + j, 0, win - 1);
-    float hrow[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-      hrow[r] = src[r][xs[0]] * cx[0] + src[r][xs[1]] * cx[1] + src[r][xs[2]] * cx[2] + src[r][xs[3]] * cx[3];
-#pragma unroll
-    for (int dy = 0; dy < 16; ++dy) {
-      const int Y = Y0 + dy;
-      const float sy = 0.25f * ((float)Y + 0.5f) - 0.5f;
-      const float fy = floorf(sy);
-      const int iy = (int)fy;
-      float cy[4];
-      cubic_coeffs(sy - fy, cy);
-      float v = 0.f;
-      // staged row r <-> source row clamp(sy0 + r): the clamp is already applied; Y0 is a multiple of 16, so
-      // iy - sy0 depends on dy alone (compile time): iy = Y0/4 + ((dy + 2) >> 2) - 1
-      (void)iy;
-      const int rb = ((dy + 2) >> 2) + 0;   // = iy - 1 - sy0
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v = (i == 0) ? hrow[rb + i] * cy[0] : v + hrow[rb + i] * cy[i];
-      o0[(size_t)Y * hr + X] = v;
-      float nv = nt[(size_t)Y * gm.ndvi_row + X];
-      if (clip_ndvi) nv = fminf(fmaxf(nv, -1.f), 1.f);
-      o1[(size_t)Y * hr + X] = (nv - mean_ndvi) * istd_ndvi;
-    }
-  }
+  tile_prepare_rows(lst + ty * gm.lst_step_y + tx * gm.lst_step_x, ndvi + ty * gm.ndvi_step_y + tx * gm.ndvi_step_x, gm.lst_row,
+                    gm.ndvi_row, x + ((size_t)t * 2 + 0) * hr * hr, x + ((size_t)t * 2 + 1) * hr * hr, src, win, blockIdx.y * 16,
+                    mean_lst, istd_lst, mean_ndvi, istd_ndvi, clip_ndvi);
 }
 
 __global__ __launch_bounds__(256) void tiles_paste_kernel(const float* __restrict__ sr, float* __restrict__ out, int T,

@@ -5,7 +5,10 @@ model -- ``ModisDatasetB.__getitem__`` (dataset.py:134-142) and the block loop o
     NDVI clip to [-1, 1] (predict.py:88-89) + z-score -> torch.cat((lst_up, ndvi), 1)
 
 fused into one kernel (``sifsr_tiles_prepare``), plus the paste-back with ``* std + mean``
-(``sifsr_tiles_paste``, predict.py:101-103).  OpenCV is absent in the build container, so the resampler is
+(``sifsr_tiles_paste``, predict.py:101-103).  Beyond the reference: ``overlap`` / ``cover_edges`` lay the tiles at a stride
+smaller than the window with a last tile flush to each raster edge (``tile_origins``) and ``blend_tiles`` merges their
+predictions with a normalised feathered blend, so a whole granule comes back without the zero band of the ragged edge tiles
+and without tile seams.  OpenCV is absent in the build container, so the resampler is
 pinned against ``F.interpolate(mode='bicubic', align_corners=False)`` (same A = -0.75 kernel, half-pixel
 centres and edge clamp as INTER_CUBIC); parity with cv2 itself is *unpinned*.
 """
@@ -40,20 +43,90 @@ def bicubic_up4(img):
     return prepare_tiles(img.contiguous(), ndvi)[:, 0:1]
 
 
-def granule_to_tiles(lst_g, ndvi_g, stats, window=64, clip_ndvi=True):
-    """Raw granule rasters lst_g (h,w) [K] and ndvi_g (4h,4w) -> (x (T,2,4win,4win), (tiles_y, tiles_x)) for the
-    non-overlapping full tiles of predict.py:84-95 (ragged edge tiles are skipped, as in the reference)."""
+def tile_origins(n, window=64, overlap=0, cover_edges=False):
+    """Origins (LST pixels) of the tiles along one axis of length ``n`` -- the layout of csrc/mosaic.h, restated: stride
+    ``window - overlap``, every tile that fits, and with ``cover_edges`` one last tile flush to the raster edge when the regular
+    ones do not end there.  The defaults give ``range(0, n - window + 1, window)``, the tiles of predict.py:84-95."""
+    n, window, overlap = int(n), int(window), int(overlap)
+    if window < 1 or window > 64:
+        raise _lib.SifsrError(f"window must be in 1..64, got {window}")
+    if overlap < 0 or 2 * overlap > window:
+        raise _lib.SifsrError(f"overlap must be in 0..window/2, got {overlap} for window {window}")
+    if n < window:
+        raise _lib.SifsrError(f"raster of {n} pixels is smaller than one window ({window})")
+    origins = list(range(0, n - window + 1, window - overlap))
+    if cover_edges and origins[-1] + window < n:
+        origins.append(n - window)
+    return origins
+
+
+def _mosaic_tiles(lst_shape, ndvi_shape, window, overlap, cover_edges):
+    """Validation shared by the overlapped entry points (before any launch) -> (tiles_y, tiles_x)."""
+    h, w = (int(v) for v in lst_shape)
+    if ndvi_shape is not None and tuple(ndvi_shape) != (4 * h, 4 * w):
+        raise _lib.SifsrError("ndvi granule must be 4x the LST granule")
+    if window % 4 or window < 4:
+        raise _lib.SifsrError(f"window must be a multiple of 4 in 4..64, got {window}")
+    return len(tile_origins(h, window, overlap, cover_edges)), len(tile_origins(w, window, overlap, cover_edges))
+
+
+def granule_to_tiles(lst_g, ndvi_g, stats, window=64, clip_ndvi=True, overlap=0, cover_edges=False, out=None):
+    """Raw granule rasters lst_g (h,w) [K] and ndvi_g (4h,4w) -> (x (T,2,4win,4win), (tiles_y, tiles_x)).  Defaults: the
+    non-overlapping full tiles of predict.py:84-95 (ragged edge tiles are skipped, as in the reference).  ``overlap`` /
+    ``cover_edges``: tiles at ``tile_origins`` along each axis (``sifsrx_tiles_prepare``); each tile's input is what the default
+    path gives for the same window x window block.  ``out``: a buffer of at least T tiles to write into (a captured run's
+    static input); the first T tiles of it are returned."""
     _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
     h, w = lst_g.shape
+
+    def alloc(T):
+        if out is None:
+            return torch.empty((T, 2, 4 * window, 4 * window), dtype=torch.float32, device=lst_g.device)
+        _lib.require_gpu(out, "tile buffer")
+        if out.dim() != 4 or out.shape[0] < T or tuple(out.shape[1:]) != (2, 4 * window, 4 * window):
+            raise _lib.SifsrError(f"tile buffer must hold {(T, 2, 4 * window, 4 * window)}, got {tuple(out.shape)}")
+        return out[:T]
+
+    if overlap or cover_edges:
+        ty, tx = _mosaic_tiles((h, w), ndvi_g.shape, window, overlap, cover_edges)
+        x = alloc(ty * tx)
+        _lib.call("sifsrx_tiles_prepare", lst_g, ndvi_g, x, h, w, window, overlap, 1 if cover_edges else 0,
+                  float(stats["mean_lst"]), float(stats["std_lst"]), float(stats["mean_ndvi"]), float(stats["std_ndvi"]),
+                  1 if clip_ndvi else 0, _lib.stream_ptr(lst_g.device))
+        return x, (ty, tx)
     if tuple(ndvi_g.shape) != (4 * h, 4 * w):
         raise _lib.SifsrError("ndvi granule must be 4x the LST granule")
     ty, tx = h // window, w // window
     if ty < 1 or tx < 1:
         raise _lib.SifsrError("granule smaller than one window")
-    x = torch.empty((ty * tx, 2, 4 * window, 4 * window), dtype=torch.float32, device=lst_g.device)
+    x = alloc(ty * tx)
     _lib.call("sifsr_tiles_prepare", lst_g, ndvi_g, x, ty, tx, window, h, w, 1, float(stats["mean_lst"]), float(stats["std_lst"]),
               float(stats["mean_ndvi"]), float(stats["std_ndvi"]), 1 if clip_ndvi else 0, _lib.stream_ptr(lst_g.device))
     return x, (ty, tx)
+
+
+def blend_tiles(sr, lst_shape, window, stats, overlap=0, cover_edges=False, out=None):
+    """sr (T,1,4win,4win) normalised predictions of the tiles of ``granule_to_tiles(..., overlap, cover_edges)`` -> the
+    de-normalised raster (4h,4w) [K]: a normalised feathered blend (``sifsrx_tiles_blend``; weights in include/sifsr_mosaic.h),
+    every pixel written, pixels no tile covers 0.  With both defaults: the reference's paste (``tiles_to_granule``) onto zeros."""
+    _lib.require_gpu(sr, "sr")
+    h, w = (int(v) for v in lst_shape)
+    if out is None:
+        out = torch.empty((4 * h, 4 * w), dtype=torch.float32, device=sr.device)
+    _lib.require_gpu(out, "output granule")
+    if tuple(out.shape) != (4 * h, 4 * w):
+        raise _lib.SifsrError(f"output granule must be {(4 * h, 4 * w)}, got {tuple(out.shape)}")
+    if not (overlap or cover_edges):
+        ty, tx = h // window, w // window
+        if ty < 1 or tx < 1 or tuple(sr.shape) != (ty * tx, 1, 4 * window, 4 * window):
+            raise _lib.SifsrError(f"sr must be {(ty * tx, 1, 4 * window, 4 * window)}, got {tuple(sr.shape)}")
+        return tiles_to_granule(sr, out.zero_(), (ty, tx), window, stats)
+    ty, tx = _mosaic_tiles((h, w), None, window, overlap, cover_edges)
+    if tuple(sr.shape) != (ty * tx, 1, 4 * window, 4 * window):
+        raise _lib.SifsrError(f"sr must be {(ty * tx, 1, 4 * window, 4 * window)} for this layout, got {tuple(sr.shape)}")
+    _lib.call("sifsrx_tiles_blend", sr, out, h, w, window, overlap, 1 if cover_edges else 0, float(stats["mean_lst"]),
+              float(stats["std_lst"]), _lib.stream_ptr(sr.device))
+    return out
 
 
 def tiles_to_granule(sr, out, tiles, window, stats):

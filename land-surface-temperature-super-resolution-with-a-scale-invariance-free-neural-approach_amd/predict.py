@@ -2,7 +2,8 @@
 
 The reference runs one eval-mode forward per 64x64 LST tile (batch 1) and de-normalises with
 ``* std + mean``; tiles are independent and do not overlap, so here they are stacked and pushed
-through the network in large batches (config 4 of BASELINE.json: batch 256).  HDF/GeoTIFF I/O is out
+through the network in large batches (config 4 of BASELINE.json: batch 256).  ``predict_granule`` can also lay the
+tiles with an overlap and a last tile flush to each edge and blend them (a seamless, complete raster; not in the reference).  HDF/GeoTIFF I/O is out
 of scope; inputs are the already normalised ``lst_up`` / ``ndvi`` tiles.
 """
 from __future__ import annotations
@@ -21,20 +22,37 @@ def predict_tiles(model, lst_up, ndvi, stats, batch=256):
     return out
 
 
+def _granule_forward(model, lst_g, ndvi_g, stats, window, batch, overlap, cover_edges, x=None, sr=None, out=None):
+    """prepare -> batched eval forwards -> blend, all enqueued on the current stream.  x / sr / out: static buffers of a
+    captured run (x and sr hold a whole number of batches: the tiles past the last real one are zeros and their predictions
+    are never read); None: allocated here and the last batch is as short as it is."""
+    from . import pipeline
+    h, w = lst_g.shape
+    if x is None:
+        x, _ = pipeline.granule_to_tiles(lst_g, ndvi_g, stats, window=window, clip_ndvi=True, overlap=overlap,
+                                         cover_edges=cover_edges)
+        sr = torch.empty((x.shape[0], 1, 4 * window, 4 * window), dtype=torch.float32, device=x.device)
+        n = x.shape[0]
+    else:
+        n = pipeline.granule_to_tiles(lst_g, ndvi_g, stats, window=window, clip_ndvi=True, overlap=overlap,
+                                      cover_edges=cover_edges, out=x)[0].shape[0]
+    for i in range(0, x.shape[0], batch):
+        sr[i:i + batch] = model(x[i:i + batch])
+    return pipeline.blend_tiles(sr[:n], (h, w), window, stats, overlap, cover_edges, out=out)
+
+
 @torch.inference_mode()
-def predict_granule(model, lst_g, ndvi_g, stats, window=64, batch=256):
+def predict_granule(model, lst_g, ndvi_g, stats, window=64, batch=256, overlap=0, cover_edges=False):
     """The whole block loop of predict.py:84-103 on the device: raw LST raster (h,w) [K] + raw NDVI raster
     (4h,4w) -> super-resolved LST raster (4h,4w) [K].  Tiles are cut, normalised, bicubic-upsampled and
     concatenated by one kernel, pushed through the network in batches, de-normalised and pasted by another;
-    pixels of ragged edge tiles stay 0, as in the reference (``LST_SR = np.zeros(...)``)."""
-    from . import pipeline
+    pixels of ragged edge tiles stay 0, as in the reference (``LST_SR = np.zeros(...)``).
+
+    ``overlap`` (LST pixels, 0..window/2) lays the tiles at stride ``window - overlap`` and merges their predictions with a
+    normalised feathered blend, which removes the seams between independently predicted tiles; ``cover_edges`` adds a last
+    tile flush to the bottom / right edge so that no pixel stays 0.  Both default to the reference's behaviour."""
     model.eval()
-    x, tiles = pipeline.granule_to_tiles(lst_g, ndvi_g, stats, window=window, clip_ndvi=True)
-    sr = torch.empty((x.shape[0], 1, 4 * window, 4 * window), dtype=torch.float32, device=x.device)
-    for i in range(0, x.shape[0], batch):
-        sr[i:i + batch] = model(x[i:i + batch])
-    out = torch.zeros((4 * lst_g.shape[0], 4 * lst_g.shape[1]), dtype=torch.float32, device=x.device)
-    return pipeline.tiles_to_granule(sr, out, tiles, window, stats)
+    return _granule_forward(model, lst_g, ndvi_g, stats, window, batch, overlap, cover_edges)
 
 
 def tile_granule(lst_norm, ndvi_norm, window=64):
@@ -85,3 +103,60 @@ class GraphedPredictor:
         self.x[:n, 1:2].copy_(ndvi)
         self.graph.replay()
         return self.out[:n].clone()
+
+
+class GranulePredictor:
+    """``predict_granule`` for ONE granule shape captured into a HIP graph: prepare -> batched eval forwards -> blend, on one
+    stream, replayed per granule.  All buffers are static; the tiles are padded with zero tiles to a whole number of batches
+    (every forward has the captured batch shape; the padding's predictions are not read).  ``__call__(lst_g, ndvi_g)`` copies
+    the rasters in, replays and returns a clone of the output raster -- bit-identical to the eager ``predict_granule`` with the
+    same arguments."""
+
+    def __init__(self, model, lst_shape, stats, window=64, overlap=0, cover_edges=False, batch=256, device=None):
+        from . import pipeline
+        self.model = model.eval()
+        dev = device or next(model.parameters()).device
+        h, w = (int(v) for v in lst_shape)
+        self.lst_shape, self.stats, self.window = (h, w), stats, int(window)
+        self.overlap, self.cover_edges, self.batch = int(overlap), bool(cover_edges), int(batch)
+        if self.overlap or self.cover_edges:
+            ty, tx = pipeline._mosaic_tiles((h, w), (4 * h, 4 * w), self.window, self.overlap, self.cover_edges)
+        else:
+            ty, tx = h // self.window, w // self.window
+            if ty < 1 or tx < 1:
+                raise pipeline._lib.SifsrError("granule smaller than one window")
+        if self.batch < 1:
+            raise pipeline._lib.SifsrError(f"batch must be positive, got {batch}")
+        self.tiles = (ty, tx)
+        n, hr = ty * tx, 4 * self.window
+        self.batch = min(self.batch, n)
+        padded = -(-n // self.batch) * self.batch
+        self.lst = torch.zeros((h, w), dtype=torch.float32, device=dev)
+        self.ndvi = torch.zeros((4 * h, 4 * w), dtype=torch.float32, device=dev)
+        self.x = torch.zeros((padded, 2, hr, hr), dtype=torch.float32, device=dev)
+        self.sr = torch.zeros((padded, 1, hr, hr), dtype=torch.float32, device=dev)
+        self.out = torch.zeros((4 * h, 4 * w), dtype=torch.float32, device=dev)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side), torch.inference_mode():
+            for _ in range(2):                      # warm-up: flat-buffer setup, allocator pools
+                self._run()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.inference_mode(), torch.cuda.graph(self.graph):
+            self._run()
+
+    def _run(self):
+        _granule_forward(self.model, self.lst, self.ndvi, self.stats, self.window, self.batch, self.overlap, self.cover_edges,
+                         x=self.x, sr=self.sr, out=self.out)
+
+    @torch.inference_mode()
+    def __call__(self, lst_g, ndvi_g):
+        h, w = self.lst_shape
+        if tuple(lst_g.shape) != (h, w) or tuple(ndvi_g.shape) != (4 * h, 4 * w):
+            raise ValueError(f"captured for an LST raster {(h, w)} and an NDVI raster {(4 * h, 4 * w)}; got "
+                             f"{tuple(lst_g.shape)}, {tuple(ndvi_g.shape)}")
+        self.lst.copy_(lst_g)
+        self.ndvi.copy_(ndvi_g)
+        self.graph.replay()
+        return self.out.clone()
