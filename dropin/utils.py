@@ -10,9 +10,11 @@ training scripts use, the hot-path ones on MI355X:
   us.read_JsonA/B/C, us.save_model, us.load_model  utils.py:718-826       -> plain host code
   us.upsampling                                    utils.py:163-180       -> bicubic x scale, OpenCV INTER_CUBIC semantics
                                                                              (A = -0.75, half-pixel centres, edge clamp)
+  us.TsHARP, us.ATPRK, us.AATPRK                   utils.py:1213-1253, :1588-1606 -> device kernels + host variogram fit
+                                                                             (sifsr.baselines); 2-D numpy in, float64 numpy out
 
-GeoTIFF / HDF I/O, the classical sharpening baselines and the plotting helpers (GDAL, OpenCV, rasterio: not installed,
-out of scope -- SURVEY.md §2) raise ``NotImplementedError`` naming what was asked for.
+GeoTIFF / HDF I/O, the DMS sharpener and the plotting helpers (GDAL, OpenCV, rasterio: not installed, out of scope --
+SURVEY.md §2) raise ``NotImplementedError`` naming what was asked for.
 """
 import json
 import os
@@ -81,6 +83,43 @@ def upsampling(img, scale):
     return pipeline.bicubic_up4(t[None, None])[0, 0].cpu().numpy().astype(a.dtype, copy=False)
 
 
+def _sharpen_args(name, temp_coarse, index_coarse, index_fine, scale, block_size=5):
+    if scale != 4:
+        raise NotImplementedError(f"{name}: only scale=4 (the paper's 1 km -> 250 m) has a gfx950 kernel, got scale={scale}")
+    if block_size != 5:
+        raise NotImplementedError(f"{name}: only block_size=5 (the reference's default) has a gfx950 kernel, got block_size={block_size}")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out = []
+    for what, a in (("temp_coarse", temp_coarse), ("index_coarse", index_coarse), ("index_fine", index_fine)):
+        a = np.asarray(a)
+        if a.ndim != 2:
+            raise ValueError(f"{name}: {what} must be a 2-D array, got shape {a.shape}")
+        out.append(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)[None, None])
+    return out
+
+
+def TsHARP(temp_coarse, index_coarse, index_fine, scale, min_T=285, path_image=False):
+    """utils.py:1213-1231 -> (4h,4w) float64 numpy.  ``path_image`` is accepted and ignored (the reference's writer is commented out)."""
+    from sifsr import baselines
+    lst, nc, nf = _sharpen_args("TsHARP", temp_coarse, index_coarse, index_fine, scale)
+    return baselines.tsharp(lst, nc, nf, min_T=min_T)[0, 0].cpu().numpy().astype(np.float64)
+
+
+def ATPRK(temp_coarse, index_coarse, index_fine, scale, scc, block_size=5, sill=7, ran=1000, min_T=285, path_image=False):
+    """utils.py:1234-1253 -> (4h,4w) float64 numpy; ``path_image`` accepted and ignored."""
+    from sifsr import baselines
+    lst, nc, nf = _sharpen_args("ATPRK", temp_coarse, index_coarse, index_fine, scale, block_size)
+    return baselines.atprk(lst, nc, nf, scc=scc, sill=sill, ran=ran, min_T=min_T)[0, 0].cpu().numpy().astype(np.float64)
+
+
+def AATPRK(temp_coarse, index_coarse, index_fine, scale, scc, b_radius=2, block_size=5, sill=7, ran=1000, min_T=285, path_image=False):
+    """utils.py:1588-1606 -> (4h,4w) float64 numpy; ``path_image`` accepted and ignored."""
+    from sifsr import baselines
+    lst, nc, nf = _sharpen_args("AATPRK", temp_coarse, index_coarse, index_fine, scale, block_size)
+    return baselines.aatprk(lst, nc, nf, scc=scc, b_radius=b_radius, sill=sill, ran=ran,
+                            min_T=min_T)[0, 0].cpu().numpy().astype(np.float64)
+
+
 def _read(file, keys):
     with open(file) as f:
         data = json.load(f)
@@ -123,5 +162,5 @@ def __getattr__(name):
     if name.startswith("__"):
         raise AttributeError(name)
     raise OutOfScopeAttribute(
-        f"utils.{name}: not part of the SIF-CNN-SR hot path (GDAL / OpenCV / rasterio I/O, classical baselines and plots "
+        f"utils.{name}: not part of the SIF-CNN-SR hot path (GDAL / OpenCV / rasterio I/O, the DMS sharpener and plots "
         "are out of scope of the MI355X build, SURVEY.md §2); use the reference's own utils.py for it")

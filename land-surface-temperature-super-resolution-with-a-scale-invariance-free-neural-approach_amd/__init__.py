@@ -12,6 +12,7 @@ Drop-in surface (SURVEY.md §8 b):
   metrics.psnr_skimage / ssim_skimage  <- utils.py:548-578 (on device)
   metrics.aster_metrics / gradient_strata  <- model_perf_aster_formatds.py:371-437 (per-pair table; us.gssim, utils.py:1904-2005)
   fourier.fft2_magnitude / attenuation_spectra / get_FRR / get_FRO / get_FRU  <- compare_methods.py:312-324, utils.py:598-662
+  baselines.tsharp / atprk / aatprk    <- utils.py:1213-1253, :1588-1606 (the paper's comparison methods, on device)
 
 The directory name is the repository's mandated package name (it contains '-', so it is imported
 through ``importlib`` or the ``sifsr`` alias: ``import sifsr`` at the repo root loads this package
@@ -20,7 +21,7 @@ and registers ``sifsr`` / ``sifsr.<submodule>`` as aliases of the same module ob
 import importlib
 import sys
 
-_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "predict")
+_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "predict", "baselines")
 for _m in _SUBMODULES:
     importlib.import_module(__name__ + "." + _m)
 

@@ -1,0 +1,253 @@
+"""The classical sharpening baselines the paper compares the network with, on the device:
+
+    us.TsHARP / us.ATPRK / us.AATPRK                                      utils.py:1213-1253, :1588-1606
+    scored per (lst 64x64, ndvi_down 64x64, ndvi 256x256) triple           model_perf_aster_formatds.py:205-218
+
+The data-sized parts -- the NDVI/LST regressions, the coarse residual, the empirical semivariogram and the fused unmix +
+correction pass over the fine raster -- are hand-written HIP kernels in float64 (include/sifsr_baselines.h, csrc/baselines.hip);
+the result is rounded once, at the float32 store.  What is left of ATPRK / AATPRK is small and stays on the HOST in float64
+NumPy: two fits of (sill, range) to 15 points and one 26 x 26 linear system per image.
+
+  fit 1   sill (1 - exp(-3 d / ran)) to the 15 points (d_k, Gamma_k), started from the `sill`, `ran` arguments
+  fit 2   the regularised model Gamma_ff of utils.py:944-975 -- the fine-scale exponential variogram averaged over the 16 x 16
+          fine-pixel pairs of every pair of coarse pixels of the 5 x 5 block, then accumulated per distance class, less class 0 --
+          started from fit 1's result.  (The reference divides the running class sum by the running class count after EVERY row
+          of the 25 x 25 matrix, not once at the end; the fit it runs is a fit of that model, so `regularised_model` has it.)
+  weights utils.py:1118-1182: Gamma_cc (25 x 25), Gamma_fc (16 x 25, from the centre pixel), the bordered 26 x 26 system.
+
+The reference fits with scipy.optimize.curve_fit(method='lm'); here the fits run the package's own damped least squares
+(`_damped_least_squares`, at most LM_MAX_ITER iterations; no scipy import).  Fit 1 is degenerate on residuals whose range exceeds
+the block (a valley of constant sill / ran) and where it stops depends on the optimiser, but the image does not: parity is held on
+the image and on the empirical semivariogram, never on the fitted parameters, and `variogram=` takes the fit out altogether.
+
+Transfers per call: one D2H of (B, 15) doubles (the semivariogram) and one H2D of (B, 16, 25) doubles (the weights).  With
+`variogram=` there is no D2H.  `tsharp` has neither.  CPU tensors raise SifsrError: there is no fallback.
+Index NaNs: pinned for `tsharp` (a NaN fine index stays NaN, a NaN coarse index is left out of the regression and makes its
+4 x 4 pixels NaN); in the kriging methods they are not pinned against the reference.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib
+
+KS = (0, 1, 2, 4, 5, 8, 9, 10, 13, 16, 17, 18, 20, 25, 32)       # squared coarse distances inside a 5 x 5 block
+LM_MAX_ITER = 200
+
+# ---- host geometry (scale 4, block 5), in units of the fine pixel ----------------------------------------------------------
+_RC = np.stack(np.divmod(np.arange(25), 5), 1)
+_DR = np.abs(_RC[:, None, 0] - _RC[None, :, 0])                    # (25, 25) coarse row / column offsets of block pixels i, j
+_DC = np.abs(_RC[:, None, 1] - _RC[None, :, 1])
+_CLASS = np.searchsorted(np.array(KS), _DR ** 2 + _DC ** 2)
+_MEMBER = (_CLASS[None] == np.arange(15)[:, None, None]).astype(np.float64)      # (15, 25, 25)
+_COUNT = np.cumsum(_MEMBER.sum(2), 1)                              # (15, 25) running class count after row i
+_E = np.arange(-3, 4)                                              # fine offset inside a coarse pixel pair, multiplicity 4 - |e|
+_MULT = ((4 - np.abs(_E))[:, None] * (4 - np.abs(_E))[None, :] / 256.0).ravel()
+# by translation symmetry Gamma_cc[i, j] depends on the coarse offset alone: (5, 5, 49) fine distances per offset
+_D_CC = np.sqrt((4 * np.arange(5)[:, None, None, None] + _E[None, None, :, None]) ** 2
+                + (4 * np.arange(5)[None, :, None, None] + _E[None, None, None, :]) ** 2).reshape(5, 5, 49)
+_A = np.stack(np.divmod(np.arange(16), 4), 1)                      # fine pixel a inside a coarse pixel
+_D_FC = np.sqrt((4 * (_RC[None, :, None, 0] - 2) + _A[None, None, :, 0] - _A[:, None, None, 0]) ** 2
+                + (4 * (_RC[None, :, None, 1] - 2) + _A[None, None, :, 1] - _A[:, None, None, 1]) ** 2)   # (16 a, 25 j, 16 b)
+
+
+def _expo(d, sill, ran):
+    return sill * (1.0 - np.exp(-d / (ran / 3.0)))
+
+
+def _gamma_cc(sill, ran, scc):
+    tab = (_expo(scc / 4.0 * _D_CC, sill, ran) * _MULT).sum(-1)    # (5, 5)
+    return tab[_DR, _DC]
+
+
+def regularised_model(sill, ran, scc=926.0):
+    """Gamma_ff of utils.py:944-975 at the 15 distance classes (module docstring: the running division is the reference's)."""
+    rows = np.einsum("kij,ij->ki", _MEMBER, _gamma_cc(sill, ran, scc))
+    m = np.zeros(15)
+    for i in range(25):
+        m = (m + rows[:, i]) / _COUNT[:, i]
+    return m - m[0]
+
+
+def kriging_weights(sill, ran, scc=926.0):
+    """utils.py:1118-1182: the (16, 25) weights of the 5 x 5 coarse residuals for the 16 fine pixels of the centre coarse pixel."""
+    A = np.zeros((26, 26))
+    A[:25, :25] = _gamma_cc(sill, ran, scc)
+    A[:25, 25] = A[25, :25] = 1.0
+    rhs = np.concatenate([_expo(scc / 4.0 * _D_FC, sill, ran).mean(-1), np.ones((16, 1))], 1)      # (16, 26)
+    return np.linalg.solve(A, rhs.T).T[:, :25]
+
+
+def _damped_least_squares(model, y, p0, max_iter=LM_MAX_ITER):
+    """Levenberg-Marquardt on the 2 parameters of `model`: forward-difference Jacobian, Marquardt's scaling by the largest
+    diagonal of J^T J seen so far, damping / 10 after an accepted step and x 10 after a rejected one.  Stops when an accepted step
+    lowers the cost by less than 1e-14 of it and moves the parameters by less than 1e-10 of their size, when no damping up to
+    1e12 lowers the cost, or after max_iter iterations.  -> (p, iterations)"""
+    p = np.asarray(p0, dtype=np.float64).copy()
+    r = model(p) - y
+    cost = float(r @ r)
+    mu, scale = 1e-3, np.zeros(2)
+    for it in range(max_iter):
+        J = np.empty((y.size, 2))
+        for k in range(2):
+            step = 1.5e-8 * max(abs(p[k]), 1e-300)
+            q = p.copy()
+            q[k] += step
+            J[:, k] = (model(q) - y - r) / step
+        A, g = J.T @ J, J.T @ r
+        scale = np.maximum(scale, np.diag(A))
+        accepted = False
+        while mu <= 1e12:
+            try:
+                dp = np.linalg.solve(A + mu * np.diag(np.where(scale > 0, scale, 1.0)), -g)
+            except np.linalg.LinAlgError:
+                mu *= 10.0
+                continue
+            with np.errstate(all="ignore"):
+                rn = model(p + dp) - y
+                cn = float(rn @ rn)
+            if np.isfinite(cn) and cn < cost:
+                accepted = True
+                break
+            mu *= 10.0
+        if not accepted:
+            return p, it
+        small = (cost - cn) <= 1e-14 * cost and np.all(np.abs(dp) <= 1e-10 * np.abs(p + dp))
+        p, r, cost, mu = p + dp, rn, cn, max(mu / 10.0, 1e-12)
+        if small or cost == 0.0:
+            return p, it + 1
+    return p, max_iter
+
+
+def fit_variogram(gamma_coarse, scc=926.0, sill=7.0, ran=1000.0):
+    """The two fits for ONE image: gamma_coarse (15,) -> (fit1 (2,), fit2 (2,)), each (sill, range)."""
+    y = np.asarray(gamma_coarse, dtype=np.float64)
+    d = scc * np.sqrt(np.array(KS, dtype=np.float64))
+    fit1, _ = _damped_least_squares(lambda p: _expo(d, p[0], p[1]), y, (sill, ran))
+    fit2, _ = _damped_least_squares(lambda p: regularised_model(p[0], p[1], scc), y, fit1)
+    return fit1, fit2
+
+
+# ---- device side ----------------------------------------------------------------------------------------------------------
+def _check(lst, ndvi_coarse, ndvi_fine):
+    for t, what in ((lst, "lst"), (ndvi_coarse, "ndvi_coarse"), (ndvi_fine, "ndvi_fine")):
+        if not isinstance(t, torch.Tensor):
+            raise _lib.SifsrError(f"{what} must be a device tensor, got {type(t).__name__}")
+        _lib.require_gpu(t, what)
+        if t.dim() != 4 or t.shape[1] != 1:
+            raise ValueError(f"{what}: expected (B,1,H,W), got {tuple(t.shape)}")
+    B, _, h, w = lst.shape
+    if tuple(ndvi_coarse.shape) != (B, 1, h, w):
+        raise ValueError(f"ndvi_coarse {tuple(ndvi_coarse.shape)} does not match lst {tuple(lst.shape)}")
+    if tuple(ndvi_fine.shape) != (B, 1, 4 * h, 4 * w):
+        raise ValueError(f"ndvi_fine must be exactly 4x the coarse shape ({B}, 1, {4 * h}, {4 * w}), got {tuple(ndvi_fine.shape)}")
+    if h < 5 or w < 5:
+        raise ValueError(f"the coarse image must be at least 5 x 5 (one kriging block), got {h} x {w}")
+    return B, h, w
+
+
+def _f64(shape, like):
+    return torch.empty(shape, dtype=torch.float64, device=like.device)
+
+
+def _global_fit(lst, ndvi_coarse, B, h, w, min_T, s):
+    fit = _f64((B, 2), lst)
+    _lib.call("sifsrb_linfit", lst, ndvi_coarse, fit, B, h, w, float(min_T), s)
+    return fit
+
+
+def _residual(lst, ndvi_coarse, coef, per_pixel, B, h, w, s):
+    delta = _f64((B, h, w), lst)
+    _lib.call("sifsrb_residual", lst, ndvi_coarse, coef, int(per_pixel), delta, B, h, w, s)
+    return delta
+
+
+def _semivariogram(delta, B, h, w, s):
+    nbytes = _lib.call("sifsrb_semivariogram_scratch_bytes", B, h, w)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=delta.device)
+    gamma = _f64((B, 15), delta)
+    _lib.call("sifsrb_semivariogram", delta, scratch, gamma, B, h, w, s)
+    return gamma
+
+
+def _sharpen(lst, ndvi_fine, coef, delta, lambdas, B, h, w, mode, s):
+    out = torch.empty((B, 1, 4 * h, 4 * w), dtype=torch.float32, device=lst.device)
+    _lib.call("sifsrb_sharpen", lst, ndvi_fine, coef, delta, lambdas, out, B, h, w, mode, s)
+    return out
+
+
+def semivariogram(delta):
+    """Gamma_coarse of utils.py:1008-1051: delta (B,1,h,w) float64 device tensor -> (B,15) float64 device tensor, the classes
+    scc * sqrt(KS)."""
+    if not isinstance(delta, torch.Tensor) or not delta.is_cuda:
+        raise _lib.SifsrError("semivariogram: delta must be a device tensor; there is no CPU path")
+    if delta.dtype != torch.float64 or delta.dim() != 4 or delta.shape[1] != 1:
+        raise ValueError(f"semivariogram: expected a (B,1,h,w) float64 tensor, got {tuple(delta.shape)} {delta.dtype}")
+    B, _, h, w = delta.shape
+    if h < 5 or w < 5:
+        raise ValueError(f"the coarse image must be at least 5 x 5, got {h} x {w}")
+    return _semivariogram(delta.contiguous(), B, h, w, _lib.stream_ptr(delta.device))
+
+
+def tsharp(lst, ndvi_coarse, ndvi_fine, min_T=285.0):
+    """us.TsHARP (utils.py:1213-1231): global NDVI/LST regression over the pixels above min_T, unmixing of the fine index, and the
+    coarse residual added back per coarse pixel.  -> (B,1,4h,4w) float32."""
+    B, h, w = _check(lst, ndvi_coarse, ndvi_fine)
+    s = _lib.stream_ptr(lst.device)
+    fit = _global_fit(lst, ndvi_coarse, B, h, w, min_T, s)
+    delta = _residual(lst, ndvi_coarse, fit, False, B, h, w, s)
+    return _sharpen(lst, ndvi_fine, fit, delta, None, B, h, w, 0, s)
+
+
+def _kriging(lst, ndvi_coarse, ndvi_fine, coef, per_pixel, mode, B, h, w, scc, sill, ran, variogram, return_variogram, s):
+    delta = _residual(lst, ndvi_coarse, coef, per_pixel, B, h, w, s)
+    info = {"gamma_coarse": None, "fit1": None}
+    if variogram is None:
+        gamma = _semivariogram(delta, B, h, w, s).cpu().numpy()               # the call's one D2H
+        fits = [fit_variogram(gamma[b], scc, sill, ran) for b in range(B)]
+        fit2 = np.stack([f[1] for f in fits])
+        info.update(gamma_coarse=gamma, fit1=np.stack([f[0] for f in fits]))
+    else:
+        fit2 = np.asarray(variogram.detach().cpu() if isinstance(variogram, torch.Tensor) else variogram, dtype=np.float64)
+        if fit2.shape == (2,):
+            fit2 = np.broadcast_to(fit2, (B, 2))
+        if fit2.shape != (B, 2):
+            raise ValueError(f"variogram: expected (sill, range) as a (2,) or ({B}, 2) array, got {fit2.shape}")
+    for b in range(B):
+        if not (np.isfinite(fit2[b]).all() and (fit2[b] > 0).all()):
+            raise _lib.SifsrError(f"image {b}: the fine-scale variogram (sill, range) = {tuple(fit2[b])} is not finite and positive")
+    lam = np.stack([kriging_weights(fit2[b, 0], fit2[b, 1], scc) for b in range(B)])
+    lam_d = torch.from_numpy(np.ascontiguousarray(lam)).to(lst.device)        # the call's one H2D
+    out = _sharpen(lst, ndvi_fine, coef, delta, lam_d, B, h, w, mode, s)
+    if return_variogram:
+        info.update(fit2=np.array(fit2), lambdas=lam)
+        return out, info
+    return out
+
+
+def atprk(lst, ndvi_coarse, ndvi_fine, scc=926.0, sill=7.0, ran=1000.0, min_T=285.0, variogram=None, return_variogram=False):
+    """us.ATPRK (utils.py:1234-1253): TsHARP's regression and unmixing, the residual downscaled by area-to-point kriging over
+    5 x 5 coarse blocks.  `scc`: coarse pixel size; `sill`, `ran`: start of fit 1; `variogram`: the FINAL fine-scale (sill, range),
+    (2,) or (B,2) -- skips both fits and the D2H.  return_variogram=True: also a dict with gamma_coarse (B,15) float64, fit1 and
+    fit2 (B,2), lambdas (B,16,25) (gamma_coarse and fit1 are None when `variogram` was given)."""
+    B, h, w = _check(lst, ndvi_coarse, ndvi_fine)
+    s = _lib.stream_ptr(lst.device)
+    fit = _global_fit(lst, ndvi_coarse, B, h, w, min_T, s)
+    return _kriging(lst, ndvi_coarse, ndvi_fine, fit, False, 1, B, h, w, float(scc), float(sill), float(ran), variogram,
+                    return_variogram, s)
+
+
+def aatprk(lst, ndvi_coarse, ndvi_fine, scc=926.0, b_radius=2, sill=7.0, ran=1000.0, min_T=285.0, variogram=None,
+           return_variogram=False):
+    """us.AATPRK (utils.py:1588-1606): the regression is fitted per coarse pixel over its (2 b_radius + 1)^2 window (the global
+    fit where no more than 2/3 of the window is valid, and within b_radius of a border); the rest as `atprk`."""
+    B, h, w = _check(lst, ndvi_coarse, ndvi_fine)
+    if not 1 <= int(b_radius) <= 8:
+        raise ValueError(f"b_radius must be in [1, 8], got {b_radius}")
+    s = _lib.stream_ptr(lst.device)
+    fit = _global_fit(lst, ndvi_coarse, B, h, w, min_T, s)
+    coef = _f64((B, 2, h, w), lst)
+    _lib.call("sifsrb_linfit_window", lst, ndvi_coarse, fit, coef, B, h, w, int(b_radius), float(min_T), s)
+    return _kriging(lst, ndvi_coarse, ndvi_fine, coef, True, 2, B, h, w, float(scc), float(sill), float(ran), variogram,
+                    return_variogram, s)
