@@ -13,6 +13,8 @@ Drop-in surface (SURVEY.md §8 b):
   metrics.aster_metrics / gradient_strata  <- model_perf_aster_formatds.py:371-437 (per-pair table; us.gssim, utils.py:1904-2005)
   fourier.fft2_magnitude / attenuation_spectra / get_FRR / get_FRO / get_FRU  <- compare_methods.py:312-324, utils.py:598-662
   baselines.tsharp / atprk / aatprk    <- utils.py:1213-1253, :1588-1606 (the paper's comparison methods, on device)
+  products.decode / PatchMiner / MinedPatches, dataset.MinedDataset  <- process_modis.py:38-335, data_preparation.py:32-102
+                                       (raw granule arrays -> patches + statistics.json, on device)
 
 The directory name is the repository's mandated package name (it contains '-', so it is imported
 through ``importlib`` or the ``sifsr`` alias: ``import sifsr`` at the repo root loads this package
@@ -21,7 +23,7 @@ and registers ``sifsr`` / ``sifsr.<submodule>`` as aliases of the same module ob
 import importlib
 import sys
 
-_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "predict", "baselines")
+_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "predict", "baselines", "products")
 for _m in _SUBMODULES:
     importlib.import_module(__name__ + "." + _m)
 
@@ -32,5 +34,5 @@ for _m in _SUBMODULES:
 from .model import ModelB_2  # noqa: E402,F401
 from .sif_ops import downscale_LST_SR_to_LR, get_output_ftm, sobel_bank, huber_loss, sif_loss  # noqa: E402,F401
 from .optim import FlatAdam  # noqa: E402,F401
-from .dataset import ModisDatasetB  # noqa: E402,F401
+from .dataset import ModisDatasetB, MinedDataset  # noqa: E402,F401
 from ._lib import SifsrError  # noqa: E402,F401

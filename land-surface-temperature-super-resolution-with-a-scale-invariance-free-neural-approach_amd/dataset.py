@@ -59,6 +59,35 @@ class ModisDatasetB_scale_invariance(ModisDatasetB):
         return up[0].numpy(), nd[0].numpy(), lst
 
 
+class MinedDataset(Dataset):
+    """The ``ModisDatasetB`` contract over patches mined from real granules (``sifsr.products.PatchMiner``): ``__len__``, the
+    ``.stats`` dict (``statistics.json`` of the TRAINING split, data_preparation.py:69-105, whatever `split` this dataset serves)
+    and ``__getitem__`` -> (lst (1,w,w), lst_up (1,4w,4w), ndvi (1,4w,4w)) float32 numpy, z-scored (dataset.py:134-142), so that
+    ``train.fit`` takes it unchanged.  The patches are copied to the host once, here; lst_up is the same bicubic as the synthetic
+    classes'.  For training at device rate use ``MinedPatches.loader`` instead."""
+
+    def __init__(self, mined, split="Train", stats=None):
+        self.split = split
+        self.stats = dict(stats) if stats is not None else mined.statistics("Train")
+        rows = mined.rows(split)
+        sel = torch.from_numpy(np.ascontiguousarray(rows)).to(mined.lst.device)
+        self.index = mined.index[rows]
+        self._lst = mined.lst.index_select(0, sel).cpu()
+        self._ndvi = mined.ndvi.index_select(0, sel).cpu()
+
+    def __len__(self):
+        return int(self._lst.shape[0])
+
+    def __getitem__(self, idx):
+        if idx < 0 or idx >= len(self):
+            raise IndexError(idx)
+        st = self.stats
+        lst = (self._lst[idx:idx + 1] - st["mean_lst"]) / st["std_lst"]
+        ndvi = (self._ndvi[idx] - st["mean_ndvi"]) / st["std_ndvi"]
+        lst_up = F.interpolate(lst, scale_factor=4, mode="bicubic", align_corners=False)[0]
+        return lst[0].numpy(), lst_up.numpy(), ndvi.numpy()
+
+
 def synthetic_device_batch(batch, device, seed=1234, hr=256):
     """BASELINE.md §3 bench inputs, generated once on the device: (lst, lst_up, ndvi)."""
     g = torch.Generator(device="cpu").manual_seed(seed)
