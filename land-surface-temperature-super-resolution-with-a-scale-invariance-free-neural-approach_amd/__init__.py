@@ -13,6 +13,8 @@ Drop-in surface (SURVEY.md §8 b):
   metrics.aster_metrics / gradient_strata  <- model_perf_aster_formatds.py:371-437 (per-pair table; us.gssim, utils.py:1904-2005)
   fourier.fft2_magnitude / attenuation_spectra / get_FRR / get_FRO / get_FRU  <- compare_methods.py:312-324, utils.py:598-662
   baselines.tsharp / atprk / aatprk    <- utils.py:1213-1253, :1588-1606 (the paper's comparison methods, on device)
+  gaps.fill_gaps / select_tiles / predict_granule_gaps (also in predict)  <- no counterpart: cloud / ocean / fill pixels of a granule
+                                       filled, all-gap tiles skipped, the output masked (include/sifsr_gaps.h)
   products.decode / PatchMiner / MinedPatches, dataset.MinedDataset  <- process_modis.py:38-335, data_preparation.py:32-102
                                        (raw granule arrays -> patches + statistics.json, on device)
 
@@ -23,7 +25,7 @@ and registers ``sifsr`` / ``sifsr.<submodule>`` as aliases of the same module ob
 import importlib
 import sys
 
-_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "predict", "baselines", "products")
+_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "gaps", "predict", "baselines", "products")
 for _m in _SUBMODULES:
     importlib.import_module(__name__ + "." + _m)
 

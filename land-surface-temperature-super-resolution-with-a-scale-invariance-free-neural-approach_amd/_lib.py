@@ -4,8 +4,9 @@ The signatures are parsed from ``include/sifsr_hip.h`` -- the header is the sing
 for the C ABI, and ``tests/test_capi_symbols.py`` checks that the library exports every declared
 symbol -- and from its extensions ``include/sifsr_mosaic.h`` (prefix ``sifsrx_``, same declaration style,
 gated by ``tests/test_mosaic_host.py``), ``include/sifsr_baselines.h`` (prefix ``sifsrb_``, gated by
-``tests/test_baselines_host.py``) and ``include/sifsr_products.h`` (prefix ``sifsrp_``, gated by
-``tests/test_products_host.py``).  There is NO fallback: if the library is missing or a call fails, we raise.
+``tests/test_baselines_host.py``), ``include/sifsr_products.h`` (prefix ``sifsrp_``, gated by
+``tests/test_products_host.py``) and ``include/sifsr_gaps.h`` (prefix ``sifsrg_``, gated by
+``tests/test_gaps_host.py``).  There is NO fallback: if the library is missing or a call fails, we raise.
 """
 from __future__ import annotations
 
@@ -21,6 +22,7 @@ HEADER = os.path.join(_ROOT, "include", "sifsr_hip.h")
 EXTENSION_HEADER = os.path.join(_ROOT, "include", "sifsr_mosaic.h")
 BASELINES_HEADER = os.path.join(_ROOT, "include", "sifsr_baselines.h")
 PRODUCTS_HEADER = os.path.join(_ROOT, "include", "sifsr_products.h")
+GAPS_HEADER = os.path.join(_ROOT, "include", "sifsr_gaps.h")
 # SIFSR_LIB: another build of the same C ABI (same-device A/B of kernel variants, tools/ab/); default: the in-tree library
 LIB_PATH = os.environ.get("SIFSR_LIB") or os.path.join(_HERE, "libsifsr_hip.so")
 
@@ -68,7 +70,7 @@ def lib():
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         _decls = {**parse_header(), **parse_header(EXTENSION_HEADER), **parse_header(BASELINES_HEADER),
-                  **parse_header(PRODUCTS_HEADER)}
+                  **parse_header(PRODUCTS_HEADER), **parse_header(GAPS_HEADER)}
         for name, (ret, args) in _decls.items():
             fn = getattr(handle, name)     # AttributeError if the library lacks a declared symbol
             fn.restype = ret
@@ -94,6 +96,11 @@ def declared_baseline_symbols():
 def declared_product_symbols():
     """The names ``include/sifsr_products.h`` declares (``sifsrp_*``)."""
     return sorted(parse_header(PRODUCTS_HEADER).keys())
+
+
+def declared_gap_symbols():
+    """The names ``include/sifsr_gaps.h`` declares (``sifsrg_*``)."""
+    return sorted(parse_header(GAPS_HEADER).keys())
 
 
 def _conv(v):

@@ -1,6 +1,7 @@
 // Whole-granule mosaics: the ONE definition of the overlapped tile layout, shared by the host entry points,
 // the kernels of mosaic.hip and (restated) pipeline.tile_origins, and the per-tile device body of the input pipeline that both
-// tiles_prepare_kernel (pipeline.hip) and mosaic_prepare_kernel (mosaic.hip) run.
+// tiles_prepare_kernel (pipeline.hip), mosaic_prepare_kernel (mosaic.hip) and gaps_prepare_kernel (gaps.hip) run; the feathered
+// gather of the blend, shared by mosaic.hip and gaps.hip.
 #pragma once
 #include "common.h"
 
@@ -110,6 +111,77 @@ static __device__ __forceinline__ void tile_prepare_rows(const float* __restrict
       o1[(size_t)Y * hr + X] = (nv - mean_ndvi) * istd_ndvi;
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The raster's layout on both axes, and the shape rules every launch over it shares (mosaic.hip, gaps.hip)
+// ---------------------------------------------------------------------------------------------
+struct MosaicGeom {
+  MosaicAxis ay, ax;
+  int lst_w;   // raster row stride (LST pixels)
+};
+
+// false: SIFSR_ERR_SHAPE
+inline bool mosaic_geom(int lst_h, int lst_w, int win, int overlap, int cover, MosaicGeom* gm) {
+  if (win < 4 || win > 64 || win % 4) return false;
+  gm->ay = mosaic_axis(lst_h, win, overlap, cover);
+  gm->ax = mosaic_axis(lst_w, win, overlap, cover);
+  gm->lst_w = lst_w;
+  if (gm->ay.count < 1 || gm->ax.count < 1) return false;
+  // tile counts and pixel offsets stay inside int / the grid limits (a raster of 16384^2 LST pixels is far above any granule)
+  return lst_h <= 16384 && lst_w <= 16384;
+}
+
+// Tile t of the layout -> its network input xt (2 planes of 4win x 4win): the rows [Y0, Y0 + 16) of tile_prepare_rows at the
+// tile's origin.  What mosaic_prepare_kernel (mosaic.hip) and gaps_prepare_kernel (gaps.hip) run.
+static __device__ __forceinline__ void mosaic_prepare_tile(const float* __restrict__ lst, const float* __restrict__ ndvi,
+                                                           float* __restrict__ xt, const MosaicGeom& gm, int t,
+                                                           float (*src)[64 + 1], int win, int Y0, float mean_lst, float istd_lst,
+                                                           float mean_ndvi, float istd_ndvi, int clip_ndvi) {
+  const int hr = 4 * win;
+  const int ty = t / gm.ax.count, tx = t - ty * gm.ax.count;
+  const int oy = mosaic_origin(gm.ay, ty), ox = mosaic_origin(gm.ax, tx);
+  tile_prepare_rows(lst + (size_t)oy * gm.lst_w + ox, ndvi + (size_t)(4 * oy) * (4 * gm.lst_w) + 4 * ox, gm.lst_w, 4 * gm.lst_w, xt,
+                    xt + (size_t)hr * hr, src, win, Y0, mean_lst, istd_lst, mean_ndvi, istd_ndvi, clip_ndvi);
+}
+
+// t(q) of sifsr_mosaic.h: the feather of a tile at local coordinate q in [0, W); R = 0: no feather
+static __device__ __forceinline__ float feather(int q, int W, float R) {
+  if (R == 0.f) return 1.f;
+  return fminf(1.f, fminf(((float)q + 0.5f) / R, ((float)(W - q) - 0.5f) / R));
+}
+
+// The feathered gather of the 4 output pixels [X, X + 4) of row Y (X a multiple of 4: the 4 pixels lie in the same tiles), the
+// ONE body of mosaic_blend_kernel (mosaic.hip) and gaps_blend_kernel (gaps.hip).  Tiles are visited in increasing (ky, kx);
+// slot_of(k) is the position of tile k in sr, a negative one skips the tile.  Uncovered (cover = 0 only): the reference's np.zeros.
+template <class SlotOf>
+static __device__ __forceinline__ float4 mosaic_blend4(const float* __restrict__ sr, const MosaicGeom& gm, float R, float mean,
+                                                       float std, int X, int Y, SlotOf slot_of) {
+  const int W = 4 * gm.ax.w;                    // tile side in output pixels
+  const MosaicCover cy = mosaic_cover(gm.ay, Y >> 2), cx = mosaic_cover(gm.ax, X >> 2);
+  float4 num = make_float4(0.f, 0.f, 0.f, 0.f), den = num;
+  for (int a = 0; a < cy.n; ++a) {
+    const int ky = mosaic_cover_index(cy, a);
+    const int qy = Y - 4 * mosaic_origin(gm.ay, ky);
+    const float wy = feather(qy, W, R);
+    for (int b = 0; b < cx.n; ++b) {
+      const int kx = mosaic_cover_index(cx, b);
+      const int qx = X - 4 * mosaic_origin(gm.ax, kx);
+      const int k = slot_of(ky * gm.ax.count + kx);
+      if (k < 0) continue;
+      const float4 v = ld4(sr + ((size_t)k * W + qy) * W + qx);
+      const float w0 = wy * feather(qx, W, R), w1 = wy * feather(qx + 1, W, R);
+      const float w2 = wy * feather(qx + 2, W, R), w3 = wy * feather(qx + 3, W, R);
+      num.x += w0 * v.x; num.y += w1 * v.y; num.z += w2 * v.z; num.w += w3 * v.w;
+      den.x += w0; den.y += w1; den.z += w2; den.w += w3;
+    }
+  }
+  float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (cy.n > 0 && cx.n > 0) {
+    o.x = num.x / den.x * std + mean; o.y = num.y / den.y * std + mean;
+    o.z = num.z / den.z * std + mean; o.w = num.w / den.w * std + mean;
+  }
+  return o;
 }
 
 // ---- mosaic.hip ----

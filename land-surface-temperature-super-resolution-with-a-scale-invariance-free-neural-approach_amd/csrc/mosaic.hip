@@ -4,7 +4,7 @@
 //
 //  * mosaic_prepare_kernel: tiles_prepare_kernel (pipeline.hip) with the tile's position taken from the layout; the per-tile
 //    body is the same device function, so a tile's network input does not depend on which of the two cut it.
-//  * mosaic_blend_kernel: a GATHER.  Each output pixel is covered by at most 3 x 3 tiles whose indices follow from two integer
+//  * mosaic_blend_kernel: a GATHER (body: mosaic_blend4 of mosaic.h, shared with the gap-aware blend of gaps.hip).  Each output pixel is covered by at most 3 x 3 tiles whose indices follow from two integer
 //    divisions per axis, so one thread sums its own pixels in a fixed order: no atomics, no accumulation raster and weight raster
 //    to zero, fill and divide (three more passes over the output), and bit-reproducible results.  Bandwidth-bound: every
 //    prediction element is read once per pixel it contributes to (16-byte loads, contiguous along x inside a tile), every
@@ -15,71 +15,22 @@
 
 namespace {
 
-struct MosaicGeom {
-  MosaicAxis ay, ax;
-  int lst_w;   // raster row stride (LST pixels)
-};
-
 __global__ __launch_bounds__(256) void mosaic_prepare_kernel(const float* __restrict__ lst, const float* __restrict__ ndvi,
                                                              float* __restrict__ x, const MosaicGeom gm, int win,
                                                              float mean_lst, float istd_lst, float mean_ndvi,
                                                              float istd_ndvi, int clip_ndvi) {
   __shared__ float src[8][64 + 1];
-  const int hr = 4 * win;
-  const int t = blockIdx.x;
-  const int ty = t / gm.ax.count, tx = t - ty * gm.ax.count;
-  const int oy = mosaic_origin(gm.ay, ty), ox = mosaic_origin(gm.ax, tx);
-  tile_prepare_rows(lst + (size_t)oy * gm.lst_w + ox, ndvi + (size_t)(4 * oy) * (4 * gm.lst_w) + 4 * ox, gm.lst_w, 4 * gm.lst_w,
-                    x + ((size_t)t * 2 + 0) * hr * hr, x + ((size_t)t * 2 + 1) * hr * hr, src, win, blockIdx.y * 16, mean_lst,
-                    istd_lst, mean_ndvi, istd_ndvi, clip_ndvi);
-}
-
-// t(q) of the header: the feather of a tile at local coordinate q in [0, W); R = 0: no feather
-__device__ __forceinline__ float feather(int q, int W, float R) {
-  if (R == 0.f) return 1.f;
-  return fminf(1.f, fminf(((float)q + 0.5f) / R, ((float)(W - q) - 0.5f) / R));
+  mosaic_prepare_tile(lst, ndvi, x + (size_t)blockIdx.x * 2 * (4 * win) * (4 * win), gm, blockIdx.x, src, win, blockIdx.y * 16,
+                      mean_lst, istd_lst, mean_ndvi, istd_ndvi, clip_ndvi);
 }
 
 // block = 64 x 4 threads: thread (i, j) owns output pixels [4*(64*blockIdx.x + i), +4) of row 4*blockIdx.y + j
 __global__ __launch_bounds__(256) void mosaic_blend_kernel(const float* __restrict__ sr, float* __restrict__ out,
                                                            const MosaicGeom gm, float R, float mean, float std) {
-  const int W = 4 * gm.ax.w;                    // tile side in output pixels
   const int out_w = 4 * gm.lst_w, out_h = 4 * gm.ay.n;
   const int X = 4 * (blockIdx.x * 64 + threadIdx.x), Y = blockIdx.y * 4 + threadIdx.y;
   if (X >= out_w || Y >= out_h) return;
-  const MosaicCover cy = mosaic_cover(gm.ay, Y >> 2), cx = mosaic_cover(gm.ax, X >> 2);
-  float4 num = make_float4(0.f, 0.f, 0.f, 0.f), den = num;
-  for (int a = 0; a < cy.n; ++a) {
-    const int ky = mosaic_cover_index(cy, a);
-    const int qy = Y - 4 * mosaic_origin(gm.ay, ky);
-    const float wy = feather(qy, W, R);
-    for (int b = 0; b < cx.n; ++b) {
-      const int kx = mosaic_cover_index(cx, b);
-      const int qx = X - 4 * mosaic_origin(gm.ax, kx);         // a multiple of 4: the 4 pixels lie in the same tiles
-      const float4 v = ld4(sr + ((size_t)(ky * gm.ax.count + kx) * W + qy) * W + qx);
-      const float w0 = wy * feather(qx, W, R), w1 = wy * feather(qx + 1, W, R);
-      const float w2 = wy * feather(qx + 2, W, R), w3 = wy * feather(qx + 3, W, R);
-      num.x += w0 * v.x; num.y += w1 * v.y; num.z += w2 * v.z; num.w += w3 * v.w;
-      den.x += w0; den.y += w1; den.z += w2; den.w += w3;
-    }
-  }
-  float4 o = make_float4(0.f, 0.f, 0.f, 0.f);   // uncovered (cover = 0 only): the reference's np.zeros
-  if (cy.n > 0 && cx.n > 0) {
-    o.x = num.x / den.x * std + mean; o.y = num.y / den.y * std + mean;
-    o.z = num.z / den.z * std + mean; o.w = num.w / den.w * std + mean;
-  }
-  st4(out + (size_t)Y * out_w + X, o);
-}
-
-// the shape rules the two launches share; false: SIFSR_ERR_SHAPE
-bool mosaic_geom(int lst_h, int lst_w, int win, int overlap, int cover, MosaicGeom* gm) {
-  if (win < 4 || win > 64 || win % 4) return false;
-  gm->ay = mosaic_axis(lst_h, win, overlap, cover);
-  gm->ax = mosaic_axis(lst_w, win, overlap, cover);
-  gm->lst_w = lst_w;
-  if (gm->ay.count < 1 || gm->ax.count < 1) return false;
-  // tile counts and pixel offsets stay inside int / the grid limits (a raster of 16384^2 LST pixels is far above any granule)
-  return lst_h <= 16384 && lst_w <= 16384;
+  st4(out + (size_t)Y * out_w + X, mosaic_blend4(sr, gm, R, mean, std, X, Y, [](int k) { return k; }));
 }
 
 }  // namespace

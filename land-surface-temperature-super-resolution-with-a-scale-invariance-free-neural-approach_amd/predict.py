@@ -4,11 +4,14 @@ The reference runs one eval-mode forward per 64x64 LST tile (batch 1) and de-nor
 ``* std + mean``; tiles are independent and do not overlap, so here they are stacked and pushed
 through the network in large batches (config 4 of BASELINE.json: batch 256).  ``predict_granule`` can also lay the
 tiles with an overlap and a last tile flush to each edge and blend them (a seamless, complete raster; not in the reference).  HDF/GeoTIFF I/O is out
-of scope; inputs are the already normalised ``lst_up`` / ``ndvi`` tiles.
+of scope; inputs are the already normalised ``lst_up`` / ``ndvi`` tiles.  ``predict_granule_gaps`` (sifsr/gaps.py)
+is ``predict_granule`` for granules with cloud / ocean / fill pixels: gaps filled, all-gap tiles skipped, the output masked.
 """
 from __future__ import annotations
 
 import torch
+
+from .gaps import fill_gaps, predict_granule_gaps, select_tiles  # noqa: F401  (the gap-aware path, DESIGN.md §9 f8)
 
 
 @torch.inference_mode()
@@ -110,7 +113,7 @@ class GranulePredictor:
     stream, replayed per granule.  All buffers are static; the tiles are padded with zero tiles to a whole number of batches
     (every forward has the captured batch shape; the padding's predictions are not read).  ``__call__(lst_g, ndvi_g)`` copies
     the rasters in, replays and returns a clone of the output raster -- bit-identical to the eager ``predict_granule`` with the
-    same arguments."""
+    same arguments.  There is no captured form of ``predict_granule_gaps``: a graph cannot have a data-dependent batch count."""
 
     def __init__(self, model, lst_shape, stats, window=64, overlap=0, cover_edges=False, batch=256, device=None):
         from . import pipeline
