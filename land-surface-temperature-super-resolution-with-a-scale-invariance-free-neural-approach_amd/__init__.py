@@ -15,6 +15,9 @@ Drop-in surface (SURVEY.md §8 b):
   baselines.tsharp / atprk / aatprk    <- utils.py:1213-1253, :1588-1606 (the paper's comparison methods, on device)
   gaps.fill_gaps / select_tiles / predict_granule_gaps (also in predict)  <- no counterpart: cloud / ocean / fill pixels of a granule
                                        filled, all-gap tiles skipped, the output masked (include/sifsr_gaps.h)
+  sif_ops.masked_sif_loss, products.fill_patches / MinedPatches.fill / masked_loader, train_step(valid=, n_valid=)  <- no counterpart:
+                                       training on partly valid patches (PatchMiner(coverage > 0)): per-patch fill, statistics over
+                                       valid pixels, a loss and gradient without the gap pixels (include/sifsr_masked.h)
   products.decode / PatchMiner / MinedPatches, dataset.MinedDataset  <- process_modis.py:38-335, data_preparation.py:32-102
                                        (raw granule arrays -> patches + statistics.json, on device)
 
@@ -34,7 +37,8 @@ for _m in _SUBMODULES:
     sys.modules.setdefault("sifsr." + _m, sys.modules[__name__ + "." + _m])
 
 from .model import ModelB_2  # noqa: E402,F401
-from .sif_ops import downscale_LST_SR_to_LR, get_output_ftm, sobel_bank, huber_loss, sif_loss  # noqa: E402,F401
+from .sif_ops import downscale_LST_SR_to_LR, get_output_ftm, sobel_bank, huber_loss, sif_loss, sif_loss_with_grad  # noqa: E402,F401
+from .sif_ops import masked_sif_loss, masked_sif_loss_with_grad  # noqa: E402,F401
 from .optim import FlatAdam  # noqa: E402,F401
 from .dataset import ModisDatasetB, MinedDataset  # noqa: E402,F401
 from ._lib import SifsrError  # noqa: E402,F401

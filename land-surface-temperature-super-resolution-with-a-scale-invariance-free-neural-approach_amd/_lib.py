@@ -5,8 +5,9 @@ for the C ABI, and ``tests/test_capi_symbols.py`` checks that the library export
 symbol -- and from its extensions ``include/sifsr_mosaic.h`` (prefix ``sifsrx_``, same declaration style,
 gated by ``tests/test_mosaic_host.py``), ``include/sifsr_baselines.h`` (prefix ``sifsrb_``, gated by
 ``tests/test_baselines_host.py``), ``include/sifsr_products.h`` (prefix ``sifsrp_``, gated by
-``tests/test_products_host.py``) and ``include/sifsr_gaps.h`` (prefix ``sifsrg_``, gated by
-``tests/test_gaps_host.py``).  There is NO fallback: if the library is missing or a call fails, we raise.
+``tests/test_products_host.py``), ``include/sifsr_gaps.h`` (prefix ``sifsrg_``, gated by
+``tests/test_gaps_host.py``) and ``include/sifsr_masked.h`` (prefix ``sifsrm_``, gated by
+``tests/test_masked_host.py``).  There is NO fallback: if the library is missing or a call fails, we raise.
 """
 from __future__ import annotations
 
@@ -23,6 +24,7 @@ EXTENSION_HEADER = os.path.join(_ROOT, "include", "sifsr_mosaic.h")
 BASELINES_HEADER = os.path.join(_ROOT, "include", "sifsr_baselines.h")
 PRODUCTS_HEADER = os.path.join(_ROOT, "include", "sifsr_products.h")
 GAPS_HEADER = os.path.join(_ROOT, "include", "sifsr_gaps.h")
+MASKED_HEADER = os.path.join(_ROOT, "include", "sifsr_masked.h")
 # SIFSR_LIB: another build of the same C ABI (same-device A/B of kernel variants, tools/ab/); default: the in-tree library
 LIB_PATH = os.environ.get("SIFSR_LIB") or os.path.join(_HERE, "libsifsr_hip.so")
 
@@ -70,7 +72,7 @@ def lib():
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         _decls = {**parse_header(), **parse_header(EXTENSION_HEADER), **parse_header(BASELINES_HEADER),
-                  **parse_header(PRODUCTS_HEADER), **parse_header(GAPS_HEADER)}
+                  **parse_header(PRODUCTS_HEADER), **parse_header(GAPS_HEADER), **parse_header(MASKED_HEADER)}
         for name, (ret, args) in _decls.items():
             fn = getattr(handle, name)     # AttributeError if the library lacks a declared symbol
             fn.restype = ret
@@ -101,6 +103,11 @@ def declared_product_symbols():
 def declared_gap_symbols():
     """The names ``include/sifsr_gaps.h`` declares (``sifsrg_*``)."""
     return sorted(parse_header(GAPS_HEADER).keys())
+
+
+def declared_masked_symbols():
+    """The names ``include/sifsr_masked.h`` declares (``sifsrm_*``)."""
+    return sorted(parse_header(MASKED_HEADER).keys())
 
 
 def _conv(v):

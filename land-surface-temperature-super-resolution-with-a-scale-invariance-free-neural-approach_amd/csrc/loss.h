@@ -15,3 +15,7 @@ size_t sif_loss_workspace_floats(int kind, int B, int H, int W);
 int launch_sif_loss(int kind, const float* sr, const float* lst, const float* ndvi, int B, int H, int W, float mean,
                     float std, float alpha, float gamma, const float* taps_ds, const float* taps_ftm, float* ws,
                     float* losses3, float* dsr, hipStream_t s);
+// the same two passes with a validity byte per LR pixel and the count of valid pixels on the device (include/sifsr_masked.h)
+int launch_sif_loss_masked(int kind, const float* sr, const float* lst, const unsigned char* valid, const long long* n_valid,
+                           const float* ndvi, int B, int H, int W, float mean, float std, float alpha, float gamma,
+                           const float* taps_ds, const float* taps_ftm, float* ws, float* losses3, float* dsr, hipStream_t s);

@@ -273,12 +273,24 @@ __global__ __launch_bounds__(256) void huber_partial_kernel(const float* __restr
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
-// out[j] = scale[j] * sum_k partials[k*stride + j]  (float64, fixed order); j < nout <= 4
+// the two finalisation scales of the masked loss, formed on the device from n = n_valid[0] by the divisions the host performs
+// for the unmasked one ((float)(1.0 / n1), (float)(1.0 / n2)); n <= 0: both 0, so that the losses come out 0
+__device__ __forceinline__ void masked_scales(const long long* __restrict__ n_valid, double per_lr, float* sc0, float* sc1) {
+  const long long n = n_valid[0];
+  const double n1 = (double)n, n2 = per_lr * (double)n;
+  *sc0 = n > 0 ? (float)(1.0 / n1) : 0.f;
+  *sc1 = n > 0 ? (float)(1.0 / n2) : 0.f;
+}
+
+// out[j] = scale[j] * sum_k partials[k*stride + j]  (float64, fixed order); j < nout <= 4.  n_valid != nullptr: the scales of the
+// masked loss (masked_scales) instead of sc0 / sc1
 __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restrict__ partials, int nblk, int stride,
                                                             int nout, float sc0, float sc1, float alpha,
-                                                            float* __restrict__ out) {
+                                                            float* __restrict__ out, const long long* __restrict__ n_valid,
+                                                            double per_lr) {
   __shared__ double r[2][256];
   const int tid = threadIdx.x;
+  if (n_valid != nullptr) masked_scales(n_valid, per_lr, &sc0, &sc1);
   double s0 = 0.0, s1 = 0.0;
   for (int k = tid; k < nblk; k += 256) {
     s0 += (double)partials[(size_t)k * stride];
@@ -315,15 +327,31 @@ __global__ void huber_bwd_kernel(const float* __restrict__ a, const float* __res
 //   r2             = (1-alpha)/N2 * clamp(e2)               SR2: e2 = (sr - G2 sr) - gamma (ndvi - G2 ndvi), (B,H,W)
 //                                                           SR1: e2 = sobel(sr) - gamma sobel(ndvi),        (B,H,W,4)
 // Pass B: dsr = G1^T D^T r1 + (r2 - G2^T r2)   |   dsr = G1^T D^T r1 + sobel^T r2
+//
+// MASKED (include/sifsr_masked.h): `valid` (B,H/4,W/4) marks the LR pixels that count and n = n_valid[0] is their
+// number.  N1 = n, N2 = 16 F n; an invalid LR pixel adds nothing to h1 and gets r1 = 0 (its lst is not read), the 16 HR pixels
+// under it add nothing to h2 and get r2 = 0.  dn and e2 are formed from sr / ndvi at every pixel as before, and pass B is the
+// unmasked one on these maps.  w1, w2 and the finalisation scales are formed on the device by the host's own expressions (IEEE
+// double divisions, one cast), so an all-valid mask with n = B H W / 16 reproduces the unmasked launch bit for bit; n <= 0: all 0.
+// The tile's 8 x 8 bytes of `valid` are read once, by the 64 threads that own its LR pixels.
 // ------------------------------------------------------------------------------------------------
-template <int KIND>   // 2: SR2 (gradFTM), 1: SR1 (predef filters)
+template <int KIND, bool MASKED>   // 2: SR2 (gradFTM), 1: SR1 (predef filters)
 __global__ __launch_bounds__(256) void sif_loss_fwd_kernel(const float* __restrict__ sr, const float* __restrict__ lst,
                                                            const float* __restrict__ ndvi, Taps k1, Taps k2, float mean,
                                                            float std, float gamma, float w1, float w2,
                                                            float* __restrict__ r1, float* __restrict__ r2,
-                                                           float* __restrict__ partials, int H, int W) {
+                                                           float* __restrict__ partials, int H, int W,
+                                                           const unsigned char* __restrict__ valid,
+                                                           const long long* __restrict__ n_valid, float alpha) {
   __shared__ float L[TP * LS], M[TP * LS], N[TP * LS];
   __shared__ float sh[4];
+  __shared__ unsigned char vt[64];   // MASKED: valid[] of the tile's 8 x 8 LR pixels (0 outside the image)
+  if constexpr (MASKED) {
+    const long long n = n_valid[0];
+    const double n1 = (double)n, n2 = (KIND == 1 ? 64.0 : 16.0) * (double)n;
+    w1 = n > 0 ? (float)((double)alpha / n1) : 0.f;
+    w2 = n > 0 ? (float)((1.0 - (double)alpha) / n2) : 0.f;
+  }
   const int tid = threadIdx.x, x0 = blockIdx.x * T, y0 = blockIdx.y * T;
   const int tx = tid & 31, ty = tid >> 5;
   const size_t img = (size_t)blockIdx.z * H * W;
@@ -350,12 +378,21 @@ __global__ __launch_bounds__(256) void sif_loss_fwd_kernel(const float* __restri
     for (int a = 0; a < 4; ++a)
 #pragma unroll
       for (int b = 0; b < 4; ++b) s = fmaf(k4(a) * k4(b), N[(4 * i + a) * LS + 4 * j + b], s);
+    bool ok = true;
     if (y0 / 4 + i < H / 4 && x0 / 4 + j < W / 4) {          // partial tiles: only pixels of the image count
       const size_t o = (size_t)blockIdx.z * (H / 4) * (W / 4) + (size_t)(y0 / 4 + i) * (W / 4) + x0 / 4 + j;
-      const float e = (s - mean) / std - lst[o];
-      h1 = huber_val(e);
-      r1[o] = w1 * clamp1(e);
+      if constexpr (MASKED) ok = valid[o] != 0;
+      if (ok) {
+        const float e = (s - mean) / std - lst[o];
+        h1 = huber_val(e);
+        r1[o] = w1 * clamp1(e);
+      } else {
+        r1[o] = 0.f;
+      }
+    } else {
+      ok = false;
     }
+    if constexpr (MASKED) vt[tid] = ok ? 1 : 0;
   }
   __syncthreads();
 
@@ -379,8 +416,12 @@ __global__ __launch_bounds__(256) void sif_loss_fwd_kernel(const float* __restri
       const float hn = L[(y + R) * LS + tx + R] - vpass_at(M, k2, y, tx);
       const float e = hs[r] - gamma * hn;
       if (y0 + y < H && x0 + tx < W) {
-        h2 += huber_val(e);
-        r2[img + (size_t)(y0 + y) * W + x0 + tx] = w2 * clamp1(e);
+        float hv = huber_val(e), rv = w2 * clamp1(e);
+        if constexpr (MASKED) {
+          if (vt[(y >> 2) * 8 + (tx >> 2)] == 0) hv = rv = 0.f;
+        }
+        h2 += hv;
+        r2[img + (size_t)(y0 + y) * W + x0 + tx] = rv;
       }
     }
   } else {
@@ -388,6 +429,12 @@ __global__ __launch_bounds__(256) void sif_loss_fwd_kernel(const float* __restri
     for (int r = 0; r < 4; ++r) {
       const int y = y0 + ty + 8 * r, x = x0 + tx;
       if (y >= H || x >= W) continue;
+      if constexpr (MASKED) {
+        if (vt[((ty + 8 * r) >> 2) * 8 + (tx >> 2)] == 0) {
+          st4(r2 + (img + (size_t)y * W + x) * 4, make_float4(0.f, 0.f, 0.f, 0.f));
+          continue;
+        }
+      }
       float nb[9], a[4], c[4];
       neigh9_zero(sr + img, H, W, y, x, nb);
       sobel4(nb, a);
@@ -409,11 +456,13 @@ __global__ __launch_bounds__(256) void sif_loss_fwd_kernel(const float* __restri
 
 // fin_*: the loss values (the job of loss_finalize_kernel) are reduced by workgroup (0,0,0) of THIS launch after its tile -- the
 // gradient does not depend on them (w1, w2 are constants), and a separate 7 us launch between the two passes sat on the serial chain
-template <int KIND>
+// MASKED: r1 / r2 are already zero where the mask says so; only the two scales differ (masked_scales)
+template <int KIND, bool MASKED>
 __global__ __launch_bounds__(256) void sif_loss_bwd_kernel(const float* __restrict__ r1, const float* __restrict__ r2,
                                                            Taps k1, Taps k2, float* __restrict__ dsr, int H, int W,
                                                            const float* __restrict__ fin_partials, int fin_nblk, float fin_sc0,
-                                                           float fin_sc1, float fin_alpha, float* __restrict__ fin_out) {
+                                                           float fin_sc1, float fin_alpha, float* __restrict__ fin_out,
+                                                           const long long* __restrict__ n_valid) {
   __shared__ float L[TP * LS], M[TP * LS];
   __shared__ double fin_w[4][2];
   const int tid = threadIdx.x, x0 = blockIdx.x * T, y0 = blockIdx.y * T;
@@ -460,6 +509,7 @@ __global__ __launch_bounds__(256) void sif_loss_bwd_kernel(const float* __restri
   for (int r = 0; r < 4; ++r)
     if (y0 + ty + 8 * r < H && x0 + tx < W) dsr[img + (size_t)(y0 + ty + 8 * r) * W + x0 + tx] = acc[r];
   if (fin_out != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {   // (workgroup-uniform)
+    if constexpr (MASKED) masked_scales(n_valid, KIND == 1 ? 64.0 : 16.0, &fin_sc0, &fin_sc1);
     double s0 = 0.0, s1 = 0.0;
     for (int k = tid; k < fin_nblk; k += 256) { s0 += (double)fin_partials[2 * (size_t)k]; s1 += (double)fin_partials[2 * (size_t)k + 1]; }
 #pragma unroll
@@ -524,7 +574,7 @@ int huber_partial_blocks(size_t n) { size_t b = (n + 4095) / 4096; return (int)(
 int launch_huber_fwd(const float* a, const float* b, float bscale, size_t n, float* partials, float* out, hipStream_t s) {
   const int nblk = huber_partial_blocks(n);
   hipLaunchKernelGGL(huber_partial_kernel, dim3(nblk), dim3(256), 0, s, a, b, bscale, n, partials);
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, s, partials, nblk, 1, 1, (float)(1.0 / (double)n), 0.f, 0.f, out);
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, s, partials, nblk, 1, 1, (float)(1.0 / (double)n), 0.f, 0.f, out, (const long long*)nullptr, 0.0);
   SIFSR_LAUNCH_CHECK();
   return SIFSR_OK;
 }
@@ -539,31 +589,53 @@ size_t sif_loss_workspace_floats(int kind, int B, int H, int W) {
   return lr + (kind == 1 ? 4 * hr : hr) + 2 * nblk;
 }
 
+namespace {
+
+template <int KIND, bool MASKED>
+void sif_loss_launch(const float* sr, const float* lst, const unsigned char* valid, const long long* n_valid, const float* ndvi,
+                     int B, int H, int W, float mean, float std, float alpha, float gamma, const Taps& k1, const Taps& k2,
+                     float* ws, float* losses3, float* dsr, hipStream_t s) {
+  const size_t hr = (size_t)B * H * W, lr = hr / 16;
+  const int nblk = B * ((H + T - 1) / T) * ((W + T - 1) / T);
+  float* r1 = ws;
+  float* r2 = r1 + lr;
+  float* partials = r2 + (KIND == 1 ? 4 * hr : hr);
+  // unmasked: the weights and scales are host constants; MASKED: the kernels form them from n_valid[0] (these are ignored)
+  const double n1 = (double)lr, n2 = KIND == 1 ? 4.0 * (double)hr : (double)hr;
+  const float w1 = (float)((double)alpha / n1), w2 = (float)((1.0 - (double)alpha) / n2);
+  const dim3 grid = SIFSR_TGRID(H, W, B);
+  hipLaunchKernelGGL((sif_loss_fwd_kernel<KIND, MASKED>), grid, dim3(256), 0, s, sr, lst, ndvi, k1, k2, mean, std, gamma, w1, w2, r1,
+                     r2, partials, H, W, valid, n_valid, alpha);
+  if (dsr != nullptr)
+    hipLaunchKernelGGL((sif_loss_bwd_kernel<KIND, MASKED>), grid, dim3(256), 0, s, r1, r2, k1, k2, dsr, H, W, partials, nblk,
+                       (float)(1.0 / n1), (float)(1.0 / n2), alpha, losses3, n_valid);
+  else
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, s, partials, nblk, 2, 2, (float)(1.0 / n1), (float)(1.0 / n2),
+                       alpha, losses3, n_valid, KIND == 1 ? 64.0 : 16.0);
+}
+
+}  // namespace
+
 int launch_sif_loss(int kind, const float* sr, const float* lst, const float* ndvi, int B, int H, int W, float mean,
                     float std, float alpha, float gamma, const float* taps_ds, const float* taps_ftm, float* ws,
                     float* losses3, float* dsr, hipStream_t s) {
   SIFSR_CHECK_ANY(H, W, 4);
   if (kind != 1 && kind != 2) return SIFSR_ERR_ARG;
-  const size_t hr = (size_t)B * H * W, lr = hr / 16;
-  const int nblk = B * ((H + T - 1) / T) * ((W + T - 1) / T);
-  float* r1 = ws;
-  float* r2 = r1 + lr;
-  float* partials = r2 + (kind == 1 ? 4 * hr : hr);
-  const double n1 = (double)lr, n2 = kind == 1 ? 4.0 * (double)hr : (double)hr;
-  const float w1 = (float)((double)alpha / n1), w2 = (float)((1.0 - (double)alpha) / n2);
   const Taps k1 = make_taps(taps_ds), k2 = make_taps(taps_ftm);
-  const dim3 grid = SIFSR_TGRID(H, W, B);
-  if (kind == 2) {
-    hipLaunchKernelGGL((sif_loss_fwd_kernel<2>), grid, dim3(256), 0, s, sr, lst, ndvi, k1, k2, mean, std, gamma, w1, w2, r1, r2, partials, H, W);
-  } else {
-    hipLaunchKernelGGL((sif_loss_fwd_kernel<1>), grid, dim3(256), 0, s, sr, lst, ndvi, k1, k2, mean, std, gamma, w1, w2, r1, r2, partials, H, W);
-  }
-  if (dsr != nullptr) {
-    if (kind == 2) hipLaunchKernelGGL((sif_loss_bwd_kernel<2>), grid, dim3(256), 0, s, r1, r2, k1, k2, dsr, H, W, partials, nblk, (float)(1.0 / n1), (float)(1.0 / n2), alpha, losses3);
-    else hipLaunchKernelGGL((sif_loss_bwd_kernel<1>), grid, dim3(256), 0, s, r1, r2, k1, k2, dsr, H, W, partials, nblk, (float)(1.0 / n1), (float)(1.0 / n2), alpha, losses3);
-  } else {
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, s, partials, nblk, 2, 2, (float)(1.0 / n1), (float)(1.0 / n2), alpha, losses3);
-  }
+  if (kind == 2) sif_loss_launch<2, false>(sr, lst, nullptr, nullptr, ndvi, B, H, W, mean, std, alpha, gamma, k1, k2, ws, losses3, dsr, s);
+  else sif_loss_launch<1, false>(sr, lst, nullptr, nullptr, ndvi, B, H, W, mean, std, alpha, gamma, k1, k2, ws, losses3, dsr, s);
+  SIFSR_LAUNCH_CHECK();
+  return SIFSR_OK;
+}
+
+int launch_sif_loss_masked(int kind, const float* sr, const float* lst, const unsigned char* valid, const long long* n_valid,
+                           const float* ndvi, int B, int H, int W, float mean, float std, float alpha, float gamma,
+                           const float* taps_ds, const float* taps_ftm, float* ws, float* losses3, float* dsr, hipStream_t s) {
+  SIFSR_CHECK_ANY(H, W, 4);
+  if (kind != 1 && kind != 2) return SIFSR_ERR_ARG;
+  const Taps k1 = make_taps(taps_ds), k2 = make_taps(taps_ftm);
+  if (kind == 2) sif_loss_launch<2, true>(sr, lst, valid, n_valid, ndvi, B, H, W, mean, std, alpha, gamma, k1, k2, ws, losses3, dsr, s);
+  else sif_loss_launch<1, true>(sr, lst, valid, n_valid, ndvi, B, H, W, mean, std, alpha, gamma, k1, k2, ws, losses3, dsr, s);
   SIFSR_LAUNCH_CHECK();
   return SIFSR_OK;
 }

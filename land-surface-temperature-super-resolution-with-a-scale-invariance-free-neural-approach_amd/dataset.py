@@ -64,15 +64,24 @@ class MinedDataset(Dataset):
     ``.stats`` dict (``statistics.json`` of the TRAINING split, data_preparation.py:69-105, whatever `split` this dataset serves)
     and ``__getitem__`` -> (lst (1,w,w), lst_up (1,4w,4w), ndvi (1,4w,4w)) float32 numpy, z-scored (dataset.py:134-142), so that
     ``train.fit`` takes it unchanged.  The patches are copied to the host once, here; lst_up is the same bicubic as the synthetic
-    classes'.  For training at device rate use ``MinedPatches.loader`` instead."""
+    classes'.  For training at device rate use ``MinedPatches.loader`` instead.
 
-    def __init__(self, mined, split="Train", stats=None):
-        self.split = split
-        self.stats = dict(stats) if stats is not None else mined.statistics("Train")
+    ``masked`` (patches mined with coverage > 0): items of five, (lst, lst_up, ndvi, valid (1,w,w) uint8, count
+    int64) -- lst is the z-scored FILLED patch (``MinedPatches.fill``), count the number of its valid pixels; the default collate
+    gives a (b,) count vector, which ``train.train_epoch`` / ``eval_epoch`` sum on the device.  The default ``stats`` are then
+    ``mined.statistics("Train", valid_only=True)``."""
+
+    def __init__(self, mined, split="Train", stats=None, masked=False):
+        self.split, self.masked = split, bool(masked)
+        self.stats = dict(stats) if stats is not None else mined.statistics("Train", valid_only=self.masked)
         rows = mined.rows(split)
         sel = torch.from_numpy(np.ascontiguousarray(rows)).to(mined.lst.device)
         self.index = mined.index[rows]
-        self._lst = mined.lst.index_select(0, sel).cpu()
+        if self.masked:
+            mined.fill()
+            self._valid = mined.valid.index_select(0, sel).cpu()
+            self._count = mined.valid_moments[rows, 0].astype(np.int64)
+        self._lst = (mined.filled if self.masked else mined.lst).index_select(0, sel).cpu()
         self._ndvi = mined.ndvi.index_select(0, sel).cpu()
 
     def __len__(self):
@@ -85,6 +94,8 @@ class MinedDataset(Dataset):
         lst = (self._lst[idx:idx + 1] - st["mean_lst"]) / st["std_lst"]
         ndvi = (self._ndvi[idx] - st["mean_ndvi"]) / st["std_ndvi"]
         lst_up = F.interpolate(lst, scale_factor=4, mode="bicubic", align_corners=False)[0]
+        if self.masked:
+            return lst[0].numpy(), lst_up.numpy(), ndvi.numpy(), self._valid[idx].numpy(), self._count[idx]
         return lst[0].numpy(), lst_up.numpy(), ndvi.numpy()
 
 

@@ -15,6 +15,11 @@ Transfers: `PatchMiner.add` has none (everything is enqueued on the current stre
 windows); `PatchMiner.finish` reads each granule's accepted count, index and moment rows back once.  CPU-only use raises
 SifsrError: there is no fallback.
 
+Partly valid patches (`PatchMiner(coverage > 0)`; include/sifsr_masked.h): `fill_patches` / `MinedPatches.fill` mark
+the valid pixels of every patch, fill the others with a neutral local mean (the fill of `gaps.fill_gaps`, per patch) and return the
+moments of the valid pixels; `statistics(valid_only=True)` merges those, and `masked_loader` yields the filled input with the mask
+and the count of valid pixels for `train.train_step(..., valid, n_valid)`.
+
 Window order and `k` are the reference generator's (us.split), see the header: on a square raster column blocks are outer, row
 blocks inner, and the ragged edge windows are counted but never accepted.
 """
@@ -79,6 +84,24 @@ def decode(lst_raw, nir, red, clip=False):
     ndvi = torch.empty((4 * h, 4 * w), dtype=torch.float32, device=lst_raw.device)
     _lib.call("sifsrp_decode", lst_raw, nir, red, lst_k, ndvi, h, w, 1 if clip else 0, _lib.stream_ptr(lst_raw.device))
     return lst_k, ndvi
+
+
+def fill_patches(lst):
+    """lst (N,1,w,w) or (N,w,w) [K], 4 <= w <= 64, w % 4 == 0 -> (filled like lst float32, valid like lst uint8 of 0 / 1,
+    moments (N,5) float64 device tensor [count, mean, M2, min, max] over the valid pixels of each patch; an empty patch:
+    [0, 0, 0, +inf, -inf]).  valid: finite and not 0 K; filled[n] is `gaps.fill_gaps(lst[n])` bit for bit (`sifsrm_patches_fill`:
+    one workgroup per patch, nothing read back)."""
+    _lib.require_gpu(lst, "lst patches")
+    if lst.dim() not in (3, 4) or (lst.dim() == 4 and lst.shape[1] != 1) or lst.shape[0] < 1 or lst.shape[-1] != lst.shape[-2]:
+        raise _lib.SifsrError(f"lst patches: expected (N,1,w,w) or (N,w,w), got {tuple(lst.shape)}")
+    n, w = int(lst.shape[0]), int(lst.shape[-1])
+    if w < 4 or w > 64 or w % 4:
+        raise _lib.SifsrError(f"lst patches: the window must be a multiple of 4 in [4, 64], got {w}")
+    filled = torch.empty_like(lst)
+    valid = torch.empty(lst.shape, dtype=torch.uint8, device=lst.device)
+    moments = torch.empty((n, 5), dtype=torch.float64, device=lst.device)
+    _lib.call("sifsrm_patches_fill", lst, filled, valid, moments, n, w, _lib.stream_ptr(lst.device))
+    return filled, valid, moments
 
 
 class PatchMiner:
@@ -159,11 +182,24 @@ def merge_moments(count, mean, m2):
 
 class MinedPatches:
     """lst (N,1,w,w) Kelvin and ndvi (N,1,4w,4w) in [-1,1], float32 device tensors; index (N,4) int64 [granule id, k, row0, col0];
-    moments (N,8) float64 (the rows of sifsrp_gather); split: None until `assign_split`, then an (N,) array of 'Train' / 'Val'."""
+    moments (N,8) float64 (the rows of sifsrp_gather); split: None until `assign_split`, then an (N,) array of 'Train' / 'Val'.
+    After `fill()`: filled (N,1,w,w) float32 and valid (N,1,w,w) uint8 device tensors, valid_moments (N,5) float64 on the host
+    ([count, mean, M2, min, max] over the valid pixels of each patch)."""
 
     def __init__(self, lst, ndvi, index, moments, window=64):
         self.lst, self.ndvi, self.index, self.moments, self.window = lst, ndvi, index, moments, int(window)
         self.split = None
+        self.filled = self.valid = self.valid_moments = self._valid_counts = None
+
+    def fill(self):
+        """`fill_patches` over all patches, once: sets and caches `.filled`, `.valid`, `.valid_moments` (one read-back of 40 bytes
+        per patch; the counts also stay on the device for the masked loader).  Returns self."""
+        if self.filled is None:
+            filled, valid, moments = fill_patches(self.lst)
+            self._valid_counts = moments[:, 0].to(torch.int64)
+            self.valid_moments = moments.cpu().numpy()
+            self.filled, self.valid = filled, valid
+        return self
 
     def __len__(self):
         return int(self.index.shape[0])
@@ -183,31 +219,51 @@ class MinedPatches:
             self.assign_split()
         return np.nonzero(self.split == split)[0]
 
-    def statistics(self, split="Train"):
+    def statistics(self, split="Train", valid_only=False):
         """statistics.json of data_preparation.py:85-102 over the patches of `split`: maxi, mini, mean_lst, std_lst, mean_ndvi,
-        std_ndvi (population standard deviations, as np.std), merged from the per-patch moments."""
-        m = self.moments[self.rows(split)]
+        std_ndvi (population standard deviations, as np.std), merged from the per-patch moments.  `valid_only`: the four LST
+        numbers over the VALID pixels only (the moments of `fill()`, merged in patch order as the others are) -- what patches
+        mined with coverage > 0 need, whose 0 K pixels would otherwise count; the NDVI numbers are unchanged."""
+        rows = self.rows(split)
+        m = self.moments[rows]
         if m.shape[0] == 0:
             raise _lib.SifsrError(f"statistics: no patch in split {split!r}")
         n, mean_l, m2_l = merge_moments(m[:, 0], m[:, 1], m[:, 2])
+        maxi, mini = float(m[:, 4].max()), float(m[:, 3].min())
+        if valid_only:
+            v = self.fill().valid_moments[rows]
+            n, mean_l, m2_l = merge_moments(v[:, 0], v[:, 1], v[:, 2])
+            if n == 0:
+                raise _lib.SifsrError(f"statistics: no valid LST pixel in split {split!r}")
+            maxi, mini = float(v[:, 4].max()), float(v[:, 3].min())
         nn, mean_n, m2_n = merge_moments(16.0 * m[:, 0], m[:, 5], m[:, 6])
-        return {"maxi": float(m[:, 4].max()), "mini": float(m[:, 3].min()), "mean_lst": float(mean_l),
+        return {"maxi": maxi, "mini": mini, "mean_lst": float(mean_l),
                 "std_lst": float(math.sqrt(m2_l / n)), "mean_ndvi": float(mean_n), "std_ndvi": float(math.sqrt(m2_n / nn))}
 
     def loader(self, split, batch, stats, shuffle=True, seed=0):
         return PatchLoader(self, split, batch, stats, shuffle, seed)
 
+    def masked_loader(self, split, batch, stats, shuffle=True, seed=0):
+        """`loader` for partly valid patches: a `PatchLoader(masked=True)` (`stats` should be `statistics(valid_only=True)`)."""
+        return PatchLoader(self, split, batch, stats, shuffle, seed, masked=True)
+
 
 class PatchLoader:
     """An iterable of device batches (lst_norm (b,1,w,w), lst_up (b,1,4w,4w), ndvi_norm (b,1,4w,4w)) -- what `train.train_epoch` /
     `train.eval_epoch` iterate over: lst_norm = (lst - mean_lst) / std_lst, lst_up its bicubic x4 (`pipeline.prepare_tiles`, the
-    resampler of the whole package) and ndvi_norm = (ndvi - mean_ndvi) / std_ndvi.  Every epoch (every `iter`) draws a new seeded permutation."""
+    resampler of the whole package) and ndvi_norm = (ndvi - mean_ndvi) / std_ndvi.  Every epoch (every `iter`) draws a new seeded permutation.
 
-    def __init__(self, mined, split, batch, stats, shuffle=True, seed=0):
+    `masked`: batches of five, (lst_norm, lst_up, ndvi_norm, valid (b,1,w,w) uint8, n_valid): lst_norm is the z-scored FILLED patch
+    (`MinedPatches.fill`), lst_up its bicubic x4, and n_valid a 0-d int64 device tensor, the number of valid LST pixels of the batch
+    -- the sum of the selected rows' counts, formed on the device without a host read."""
+
+    def __init__(self, mined, split, batch, stats, shuffle=True, seed=0, masked=False):
         self.mined, self.rows, self.batch, self.stats = mined, mined.rows(split), int(batch), dict(stats)
-        self.shuffle, self.seed, self.epoch = bool(shuffle), int(seed), 0
+        self.shuffle, self.seed, self.epoch, self.masked = bool(shuffle), int(seed), 0, bool(masked)
         if self.batch < 1:
             raise ValueError(f"batch must be positive, got {batch}")
+        if self.masked:
+            mined.fill()
 
     def __len__(self):
         return -(-len(self.rows) // self.batch)
@@ -221,7 +277,11 @@ class PatchLoader:
         m, st = self.mined, self.stats
         for a in range(0, len(rows), self.batch):
             sel = torch.from_numpy(np.ascontiguousarray(rows[a:a + self.batch])).to(m.lst.device)
-            lst = (m.lst.index_select(0, sel) - float(st["mean_lst"])) / float(st["std_lst"])
+            src = m.filled if self.masked else m.lst
+            lst = (src.index_select(0, sel) - float(st["mean_lst"])) / float(st["std_lst"])
             ndvi = (m.ndvi.index_select(0, sel) - float(st["mean_ndvi"])) / float(st["std_ndvi"])
             x = pipeline.prepare_tiles(lst, ndvi)                       # unit statistics: channel 0 = bicubic x4 of lst
-            yield lst, x[:, 0:1].contiguous(), ndvi
+            if self.masked:
+                yield lst, x[:, 0:1].contiguous(), ndvi, m.valid.index_select(0, sel), m._valid_counts.index_select(0, sel).sum()
+            else:
+                yield lst, x[:, 0:1].contiguous(), ndvi

@@ -5,7 +5,8 @@ reference signatures and return autograd-capable tensors on ``data.device``; the
 hand-written gfx950 kernels behind the C ABI (include/sifsr_hip.h).  ``sif_loss`` is the fused form
 of the whole loss block of the two training scripts (train_model_B_gradFTM.py:99-117,
 train_model_B_predef_filters.py:111-133): two launches for the three loss values and one for
-d loss / d sr.  No CPU path.
+d loss / d sr.  ``masked_sif_loss`` is the same block for partly valid patches (include/sifsr_masked.h): an LR
+pixel marked invalid contributes nothing to either term or to the gradient.  No CPU path.
 """
 from __future__ import annotations
 
@@ -216,3 +217,75 @@ def sif_loss(kind, sr, lst, ndvi, mean, std, alpha, gamma):
     kind='sr1': train_model_B_predef_filters.py:111-133.  Returns (ds_loss, percep_loss, loss) as
     0-d device tensors; only ``loss`` carries a gradient (to ``sr``)."""
     return _SifLoss.apply(sr.contiguous(), lst.contiguous(), ndvi.contiguous(), kind, mean, std, alpha, gamma)
+
+
+# ---- the masked form: training on partly valid patches (include/sifsr_masked.h) -------------------------------------------------
+def _masked_args(sr, lst, valid, n_valid, ndvi):
+    for t, n in ((sr, "sr"), (lst, "lst"), (ndvi, "ndvi")):
+        _lib.require_gpu(t, n)
+    B, C, H, W = sr.shape
+    if C != 1 or tuple(ndvi.shape) != (B, 1, H, W) or tuple(lst.shape) != (B, 1, H // 4, W // 4):
+        raise _lib.SifsrError("masked_sif_loss expects sr (B,1,H,W), lst (B,1,H/4,W/4), ndvi (B,1,H,W)")
+    if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.uint8, torch.bool):
+        raise _lib.SifsrError(f"valid must be a uint8 or bool tensor, got {getattr(valid, 'dtype', type(valid).__name__)}")
+    if valid.device != sr.device:
+        raise _lib.SifsrError(f"valid is on {valid.device}, sr on {sr.device}")
+    if tuple(valid.shape) not in ((B, 1, H // 4, W // 4), (B, H // 4, W // 4)):
+        raise _lib.SifsrError(f"valid must be {(B, 1, H // 4, W // 4)} (one byte per LR pixel), got {tuple(valid.shape)}")
+    valid = valid.contiguous().view(torch.uint8)
+    if not isinstance(n_valid, torch.Tensor):
+        n_valid = torch.tensor(int(n_valid), dtype=torch.int64, device=sr.device)
+    if n_valid.dtype != torch.int64 or n_valid.numel() != 1 or n_valid.device != sr.device:
+        raise _lib.SifsrError("n_valid must be one int64 on the device of sr (the number of valid LR pixels of the batch)")
+    return B, H, W, valid, n_valid.contiguous()
+
+
+def _masked_call(k, sr, lst, valid, n_valid, ndvi, B, H, W, mean, std, alpha, gamma, with_grad):
+    ws_bytes = _lib.call("sifsrm_sif_loss_workspace_bytes", k, B, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=sr.device)
+    losses = torch.empty(3, dtype=torch.float32, device=sr.device)
+    dsr = torch.empty_like(sr) if with_grad else None
+    _lib.call("sifsrm_sif_loss", k, sr, lst, valid, n_valid, ndvi, B, H, W, float(mean), float(std), float(alpha), float(gamma),
+              _taps_c(0.1, 4, None), _taps_c(0.25, 4, None), ws, ws_bytes, losses, dsr, _lib.stream_ptr(sr.device))
+    return losses, dsr
+
+
+class _MaskedSifLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sr, lst, valid, n_valid, ndvi, kind, mean, std, alpha, gamma):
+        B, H, W, valid, n_valid = _masked_args(sr, lst, valid, n_valid, ndvi)
+        losses, dsr = _masked_call({"sr2": 2, "sr1": 1}[kind], sr, lst, valid, n_valid, ndvi, B, H, W, mean, std, alpha, gamma,
+                                   ctx.needs_input_grad[0])
+        ctx.dsr = dsr
+        ds, pl, loss = losses[0], losses[1], losses[2]
+        ctx.mark_non_differentiable(ds, pl)
+        ctx.set_materialize_grads(False)
+        return ds, pl, loss
+
+    @staticmethod
+    def backward(ctx, g_ds, g_pl, g_loss):
+        dsr = ctx.dsr
+        ctx.dsr = None
+        if g_loss is None:
+            return (None,) * 10
+        if dsr is None:
+            raise _lib.SifsrError("masked_sif_loss: backward called twice (d loss / d sr was released after the first call)")
+        return (dsr * g_loss,) + (None,) * 9
+
+
+def masked_sif_loss_with_grad(kind, sr, lst, valid, n_valid, ndvi, mean, std, alpha, gamma):
+    """``sif_loss_with_grad`` for partly valid patches: (ds_loss, percep_loss, loss, d loss / d sr) without an autograd node.
+    ``valid`` (B,1,H/4,W/4) uint8 / bool marks the LR pixels that count, ``n_valid`` is their number as one int64 ON THE DEVICE
+    (nothing is read back; an int is copied there).  With every pixel valid the result is ``sif_loss_with_grad``'s, bit for bit."""
+    srd, lst, ndvi = sr.detach().contiguous(), lst.contiguous(), ndvi.contiguous()
+    B, H, W, valid, n_valid = _masked_args(srd, lst, valid, n_valid, ndvi)
+    losses, dsr = _masked_call({"sr2": 2, "sr1": 1}[kind], srd, lst, valid, n_valid, ndvi, B, H, W, mean, std, alpha, gamma, True)
+    return losses[0], losses[1], losses[2], dsr
+
+
+def masked_sif_loss(kind, sr, lst, valid, n_valid, ndvi, mean, std, alpha, gamma):
+    """The fused loss block over the valid LR pixels only (include/sifsr_masked.h): both Huber means run over the pixels marked in
+    ``valid`` (the high-frequency term over the 16 HR pixels under each) and are divided by ``n_valid``; an invalid pixel adds
+    nothing to the losses or the gradient and its ``lst`` is never read.  Returns (ds_loss, percep_loss, loss) as 0-d device
+    tensors; only ``loss`` carries a gradient (to ``sr``).  ``n_valid`` == 0: zeros."""
+    return _MaskedSifLoss.apply(sr.contiguous(), lst.contiguous(), valid, n_valid, ndvi.contiguous(), kind, mean, std, alpha, gamma)

@@ -4,6 +4,13 @@
 
     lst_ndvi = cat(lst_up, ndvi); sr = model(lst_ndvi)
     ds, pl, loss = SIF loss(sr, lst, ndvi; mean, std, alpha, gamma);  loss.backward();  optimizer.step()
+
+Partly valid patches: with ``valid`` (b,1,w,w) and ``n_valid`` (one int64 on the device) the loss is
+``sif_ops.masked_sif_loss`` -- ``lst`` / ``lst_up`` are then the FILLED patch and its bicubic x4 (``MinedPatches.masked_loader``,
+``MinedDataset(masked=True)``), and a gap pixel contributes nothing to the loss or the gradient.  Two things are NOT gap-aware and
+stay what they are: PSNR / SSIM of an epoch are scored against the filled ``lst_up`` over all pixels, and under data-parallel
+runs each rank normalises its loss by its OWN ``n_valid`` before the gradients are averaged (as BatchNorm uses per-replica
+statistics), so ranks with few valid pixels weigh their pixels more.
 """
 from __future__ import annotations
 
@@ -13,22 +20,31 @@ import torch
 
 from . import distributed as dp
 from . import metrics as _metrics
-from .sif_ops import huber_loss, sif_loss, sif_loss_with_grad
+from .sif_ops import huber_loss, masked_sif_loss, masked_sif_loss_with_grad, sif_loss, sif_loss_with_grad
 
 
-def train_step(model, optimizer, lst, lst_up, ndvi, stats, alpha, gamma, kind="sr2", sync_grads=True, return_sr=False):
+def train_step(model, optimizer, lst, lst_up, ndvi, stats, alpha, gamma, kind="sr2", sync_grads=True, return_sr=False,
+               valid=None, n_valid=None):
     """One optimisation step.  Returns device scalars (ds_loss, percep_loss, loss) -- no host sync --
     and, with ``return_sr``, the detached training-mode prediction as a fourth item (the tensor the reference scores
     with PSNR / SSIM, train_model_B_gradFTM.py:126-127).
 
     ``stats`` is the dataset's ``.stats`` dict (the reference reads the module-global
-    ``train_ds.stats``, train_model_B_gradFTM.py:99-100)."""
+    ``train_ds.stats``, train_model_B_gradFTM.py:99-100).
+
+    ``valid`` / ``n_valid`` (both or neither): the masked loss over the valid LST pixels only (module docstring)."""
+    if (valid is None) != (n_valid is None):
+        raise ValueError("train_step: pass both valid and n_valid, or neither")
     model.train()
     optimizer.zero_grad(set_to_none=True)
     lst_ndvi = torch.cat((lst_up, ndvi), dim=1)
     sr = model(lst_ndvi)
     # loss.backward() == sr.backward(d loss / d sr): the fused loss op returns that gradient directly (sif_ops.sif_loss_with_grad)
-    ds, pl, loss, dsr = sif_loss_with_grad(kind, sr, lst, ndvi, stats["mean_lst"], stats["std_lst"], alpha, gamma)
+    if valid is None:
+        ds, pl, loss, dsr = sif_loss_with_grad(kind, sr, lst, ndvi, stats["mean_lst"], stats["std_lst"], alpha, gamma)
+    else:
+        ds, pl, loss, dsr = masked_sif_loss_with_grad(kind, sr, lst, valid, n_valid, ndvi, stats["mean_lst"], stats["std_lst"],
+                                                      alpha, gamma)
     sr.backward(dsr)
     if sync_grads:
         dp.allreduce_gradients(model, optimizer)
@@ -39,11 +55,27 @@ def train_step(model, optimizer, lst, lst_up, ndvi, stats, alpha, gamma, kind="s
 
 
 @torch.inference_mode()
-def eval_step(model, lst, lst_up, ndvi, stats, alpha, gamma, kind="sr2"):
-    """test_step semantics (train_model_B_gradFTM.py:141-237): eval mode, no gradient."""
+def eval_step(model, lst, lst_up, ndvi, stats, alpha, gamma, kind="sr2", valid=None, n_valid=None):
+    """test_step semantics (train_model_B_gradFTM.py:141-237): eval mode, no gradient.  ``valid`` / ``n_valid``: as ``train_step``."""
+    if (valid is None) != (n_valid is None):
+        raise ValueError("eval_step: pass both valid and n_valid, or neither")
     model.eval()
     sr = model(torch.cat((lst_up, ndvi), dim=1))
-    return sif_loss(kind, sr, lst, ndvi, stats["mean_lst"], stats["std_lst"], alpha, gamma)
+    if valid is None:
+        return sif_loss(kind, sr, lst, ndvi, stats["mean_lst"], stats["std_lst"], alpha, gamma)
+    return masked_sif_loss(kind, sr, lst, valid, n_valid, ndvi, stats["mean_lst"], stats["std_lst"], alpha, gamma)
+
+
+def _unpack_batch(batch, device):
+    """(lst, lst_up, ndvi) or (lst, lst_up, ndvi, valid, count) -> the five on `device`, valid / n_valid None for a batch of three;
+    a (b,) count vector (the default collate of ``MinedDataset(masked=True)``) is summed on the device, nothing is read back."""
+    if len(batch) not in (3, 5):
+        raise ValueError(f"a batch has 3 or 5 items, got {len(batch)}")
+    lst, lst_up, ndvi = (t.to(device) for t in batch[:3])
+    if len(batch) == 3:
+        return lst, lst_up, ndvi, None, None
+    valid, n_valid = batch[3].to(device), batch[4].to(device=device, dtype=torch.int64)
+    return lst, lst_up, ndvi, valid, (n_valid.sum() if n_valid.dim() else n_valid)
 
 
 def si_train_step(model, optimizer, lst_4km_up, ndvi_1km, lst_1km, sync_grads=True):
@@ -92,12 +124,14 @@ def train_epoch(model, loader, optimizer, stats, alpha, gamma, kind="sr2", devic
     (:89) and one optimisation step; returns the epoch means (ds_loss, percep_loss, loss, psnr, ssim), PSNR / SSIM of
     the training-mode prediction against ``lst_up`` as the reference scores them (:126-127) but on the device
     (``metrics.psnr_ssim``).  The per-batch scalars stay on the device and are read back ONCE per
-    epoch; the reference calls ``.item()`` three times and copies two full tensors to the host per batch."""
+    epoch; the reference calls ``.item()`` three times and copies two full tensors to the host per batch.
+    Batches of five (masked loaders / datasets) take the masked step; their PSNR / SSIM are not gap-aware (module docstring)."""
     acc = torch.zeros(5, dtype=torch.float64, device=device)
     n = 0
-    for lst, lst_up, ndvi in loader:
-        lst, lst_up, ndvi = lst.to(device), lst_up.to(device), ndvi.to(device)
-        ds, pl, loss, sr = train_step(model, optimizer, lst, lst_up, ndvi, stats, alpha, gamma, kind, return_sr=True)
+    for batch in loader:
+        lst, lst_up, ndvi, valid, n_valid = _unpack_batch(batch, device)
+        ds, pl, loss, sr = train_step(model, optimizer, lst, lst_up, ndvi, stats, alpha, gamma, kind, return_sr=True,
+                                      valid=valid, n_valid=n_valid)
         acc[0] += ds.detach(); acc[1] += pl.detach(); acc[2] += loss.detach()
         if with_metrics:
             ps, ss = _metrics.psnr_ssim(sr, lst_up)
@@ -109,14 +143,17 @@ def train_epoch(model, loader, optimizer, stats, alpha, gamma, kind="sr2", devic
 @torch.inference_mode()
 def eval_epoch(model, loader, stats, alpha, gamma, kind="sr2", device="cuda", with_metrics=True):
     """The reference's ``test_step`` (train_model_B_gradFTM.py:141-237): eval mode, no gradient; epoch means of
-    (ds_loss, percep_loss, loss, psnr, ssim)."""
+    (ds_loss, percep_loss, loss, psnr, ssim).  Batches of five: the masked loss, as in ``train_epoch``."""
     model.eval()
     acc = torch.zeros(5, dtype=torch.float64, device=device)
     n = 0
-    for lst, lst_up, ndvi in loader:
-        lst, lst_up, ndvi = lst.to(device), lst_up.to(device), ndvi.to(device)
+    for batch in loader:
+        lst, lst_up, ndvi, valid, n_valid = _unpack_batch(batch, device)
         sr = model(torch.cat((lst_up, ndvi), dim=1))
-        ds, pl, loss = sif_loss(kind, sr, lst, ndvi, stats["mean_lst"], stats["std_lst"], alpha, gamma)
+        if valid is None:
+            ds, pl, loss = sif_loss(kind, sr, lst, ndvi, stats["mean_lst"], stats["std_lst"], alpha, gamma)
+        else:
+            ds, pl, loss = masked_sif_loss(kind, sr, lst, valid, n_valid, ndvi, stats["mean_lst"], stats["std_lst"], alpha, gamma)
         acc[0] += ds; acc[1] += pl; acc[2] += loss
         if with_metrics:
             ps, ss = _metrics.psnr_ssim(sr, lst_up)
@@ -160,9 +197,11 @@ class GraphedTrainStep:
     the loss and optimizer launches; none allocates outside torch's graph pool, synchronises, or reads a host value that
     changes between steps (``FlatAdam(capturable=True)`` keeps its step count on the device), so replay removes the
     host cost of ~190 launches per step.  That matters at small batch (at batch 64 the GPU is the bottleneck).
-    Single GPU: the gradient all-reduce of data-parallel runs is not part of the captured region."""
+    Single GPU: the gradient all-reduce of data-parallel runs is not part of the captured region.
+    ``masked``: the masked step; two more static buffers (``valid`` (batch,1,hr/4,hr/4) uint8, ``n_valid`` one int64) are copied
+    into per call -- the masked loss reads the count on the device, so the captured graph serves every mask."""
 
-    def __init__(self, model, optimizer, batch, stats, alpha, gamma, kind="sr2", hr=256, device=None):
+    def __init__(self, model, optimizer, batch, stats, alpha, gamma, kind="sr2", hr=256, device=None, masked=False):
         if not getattr(optimizer, "capturable", False):
             raise ValueError("GraphedTrainStep needs FlatAdam(..., capturable=True)")
         dev = device or next(model.parameters()).device
@@ -170,13 +209,17 @@ class GraphedTrainStep:
         self.lst = torch.zeros((batch, 1, hr // 4, hr // 4), dtype=torch.float32, device=dev)
         self.lst_up = torch.zeros((batch, 1, hr, hr), dtype=torch.float32, device=dev)
         self.ndvi = torch.zeros((batch, 1, hr, hr), dtype=torch.float32, device=dev)
+        self.masked = bool(masked)
+        self.valid = torch.zeros((batch, 1, hr // 4, hr // 4), dtype=torch.uint8, device=dev) if self.masked else None
+        self.n_valid = torch.zeros((), dtype=torch.int64, device=dev) if self.masked else None
         args = (stats, alpha, gamma, kind)
 
         def step():
             # detached: a caller holding the returned loss must not keep the step's autograd graph (and with it the
             # parameters' AccumulateGrad nodes, bound to the stream they were made on) alive into the capture --
             # torch then syncs the capture stream with that stream and the capture is invalid
-            out = train_step(model, optimizer, self.lst, self.lst_up, self.ndvi, *args, sync_grads=False)
+            out = train_step(model, optimizer, self.lst, self.lst_up, self.ndvi, *args, sync_grads=False, valid=self.valid,
+                             n_valid=self.n_valid)
             return tuple(t.detach() for t in out)
 
         self._eager = step
@@ -184,10 +227,16 @@ class GraphedTrainStep:
         self._warm = 0
         self.out = None
 
-    def __call__(self, lst, lst_up, ndvi):
+    def __call__(self, lst, lst_up, ndvi, valid=None, n_valid=None):
         """Copies the batch into the static inputs and runs the step; returns device scalars (ds, pl, loss).  The first
-        three calls run eagerly (flat-buffer set-up, allocator pools, optimizer state), the fourth captures."""
+        three calls run eagerly (flat-buffer set-up, allocator pools, optimizer state), the fourth captures.
+        ``masked``: ``valid`` and ``n_valid`` (a device tensor: no host read) are required, otherwise refused."""
+        if self.masked != (valid is not None) or self.masked != (n_valid is not None):
+            raise ValueError("GraphedTrainStep: valid and n_valid go with masked=True, and only with it")
         self.lst.copy_(lst); self.lst_up.copy_(lst_up); self.ndvi.copy_(ndvi)
+        if self.masked:
+            self.valid.copy_(valid.reshape(self.valid.shape))
+            self.n_valid.copy_(n_valid.reshape(()) if isinstance(n_valid, torch.Tensor) else torch.tensor(int(n_valid)))
         if self.graph is not None:
             self.graph.replay()
             return self.out
