@@ -18,6 +18,8 @@ Drop-in surface (SURVEY.md §8 b):
   sif_ops.masked_sif_loss, products.fill_patches / MinedPatches.fill / masked_loader, train_step(valid=, n_valid=)  <- no counterpart:
                                        training on partly valid patches (PatchMiner(coverage > 0)): per-patch fill, statistics over
                                        valid pixels, a loss and gradient without the gap pixels (include/sifsr_masked.h)
+  metrics.masked_aster_metrics / masked_psnr_ssim, train_epoch(masked_metrics=)  <- no counterpart: both metric sets over the valid
+                                       pixels of rasters with gaps, a term counted iff its whole stencil is valid (include/sifsr_scores.h)
   products.decode / PatchMiner / MinedPatches, dataset.MinedDataset  <- process_modis.py:38-335, data_preparation.py:32-102
                                        (raw granule arrays -> patches + statistics.json, on device)
 

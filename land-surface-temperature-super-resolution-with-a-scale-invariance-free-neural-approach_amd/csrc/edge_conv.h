@@ -84,6 +84,10 @@ int launch_tiles_paste(const float* sr, float* out, int T, int tiles_x, int hr, 
 int launch_l4pool4(const float* x, float* out, int B, int H, int W, hipStream_t s);
 size_t psnr_ssim_scratch_bytes(int B, int H, int W);
 int launch_psnr_ssim(const float* pred, const float* targ, int B, int H, int W, void* scratch, float* out2, hipStream_t s);
+// the MASKED instantiations (include/sifsr_scores.h): valid (B, H/scale, W/scale), scale 1 or 4
+size_t psnr_ssim_masked_scratch_bytes(int B, int H, int W);
+int launch_psnr_ssim_masked(const float* pred, const float* targ, const unsigned char* valid, int scale, int B, int H, int W,
+                            void* scratch, float* out2, int* counts2, hipStream_t s);
 
 // ---- eval_metrics.hip ---- (per-pair ASTER evaluation metrics)
 size_t eval_metrics_scratch_bytes(int B, int H, int W);
@@ -91,6 +95,9 @@ int launch_eval_metrics(const float* a, const float* b, int B, int H, int W, con
                         void* scratch, double* out8, hipStream_t s);
 int launch_gradient_strata(const float* a, int B, int H, int W, const float* taps9, float* g, float* q2, int* counts3,
                            hipStream_t s);
+size_t eval_metrics_masked_scratch_bytes(int B, int H, int W);   // 0: unsupported shape
+int launch_eval_metrics_masked(const float* a, const float* b, const unsigned char* mask, int B, int H, int W,
+                               const float* taps9, float data_range, void* scratch, double* out8, int* counts5, hipStream_t s);
 
 // ---- fourier.hip ---- (Fourier-domain evaluation)
 size_t fourier_scratch_bytes(int B, int H, int W);

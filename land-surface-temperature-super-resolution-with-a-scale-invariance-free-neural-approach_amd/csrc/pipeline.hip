@@ -9,6 +9,10 @@
 //  * psnr / ssim: us.psnr_skimage / us.ssim_skimage (utils.py:548-578; scikit-image 0.22 defaults: 7x7 uniform
 //    window, sample covariance, K1 = 0.01, K2 = 0.03, data_range = max - min of the TARGET BATCH, mean over
 //    the window-valid interior), batch means as two device scalars -- no D2H of the images, no host stall.
+//    MASKED instantiations (include/sifsr_scores.h; entry points in scores.hip): validity is the byte of
+//    the pixel's LR cell, the range is taken over the valid target pixels, the squared error is summed over the valid
+//    pixels and the SSIM map over the pixels whose 7x7 window is all valid (separable byte counts in LDS, 3-pixel halo);
+//    selection by predicate, so that an all-valid mask adds the same values in the same order as the unmasked kernels.
 #include "edge_conv.h"
 #include "mosaic.h"   // tile_prepare_rows: the per-tile body shared with the overlapped layout
 
@@ -70,10 +74,18 @@ __global__ __launch_bounds__(256) void l4pool4_kernel(const float* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // PSNR / SSIM
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void minmax_partial_kernel(const float* __restrict__ t, size_t n, float* __restrict__ part) {
+template <bool MASKED>
+__global__ __launch_bounds__(256) void minmax_partial_kernel(const float* __restrict__ t, size_t n, float* __restrict__ part,
+                                                             const unsigned char* __restrict__ valid, int H, int W, int scale) {
   __shared__ float smin[256], smax[256];
   float lo = INFINITY, hi = -INFINITY;
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
+    if constexpr (MASKED) {
+      const int x = (int)(e % W);
+      const size_t r = e / W;
+      const int y = (int)(r % H);
+      if (!valid[((r / H) * (H / scale) + y / scale) * (W / scale) + x / scale]) continue;
+    }
     const float v = t[e];
     lo = fminf(lo, v); hi = fmaxf(hi, v);
   }
@@ -101,12 +113,18 @@ constexpr int MT = 32;          // SSIM output tile
 constexpr int MH = MT + 6;      // + 3-pixel halo of the 7x7 window
 
 // per (image, 32x32 tile): sum of the SSIM map over the window-valid pixels of the tile, and sum of squared error
+// MASKED: vb = the validity byte of every pixel of the 38 x 38 LDS tile (0 outside the image), hv = its horizontal 7-counts;
+// pcnt = per tile the number of valid pixels and of all-valid windows.  6.7 KB on top of 64.6 KB: two workgroups per CU as before.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void psnr_ssim_tile_kernel(const float* __restrict__ pred, const float* __restrict__ targ,
                                                              const float* __restrict__ mm, int H, int W,
-                                                             double* __restrict__ part) {
+                                                             double* __restrict__ part, const unsigned char* __restrict__ valid,
+                                                             int scale, int* __restrict__ pcnt) {
   __shared__ float a[MH][MH + 1], b[MH][MH + 1];   // a = target (im1 in skimage's call), b = prediction
   __shared__ double hs[5][MH][MT];                  // horizontal 7-sums of a, b, a*a, b*b, a*b
   __shared__ double red[256][2];
+  __shared__ unsigned char vb[MASKED ? MH : 1][MASKED ? MH : 1], hv[MASKED ? MH : 1][MASKED ? MT : 1];
+  __shared__ int redi[MASKED ? 256 : 1][2];
   const int tid = threadIdx.x;
   const int x0 = blockIdx.x * MT, y0 = blockIdx.y * MT, img = blockIdx.z;
   const float R = mm[513] - mm[512];
@@ -119,10 +137,18 @@ __global__ __launch_bounds__(256) void psnr_ssim_tile_kernel(const float* __rest
     const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
     a[r][c] = in ? tp[(size_t)gy * W + gx] : 0.f;
     b[r][c] = in ? pp[(size_t)gy * W + gx] : 0.f;
+    if constexpr (MASKED)
+      vb[r][c] = in && valid[((size_t)img * (H / scale) + gy / scale) * (W / scale) + gx / scale] != 0 ? 1 : 0;
   }
   __syncthreads();
   for (int e = tid; e < MH * MT; e += 256) {
     const int r = e / MT, c = e - r * MT;
+    if constexpr (MASKED) {
+      int n = 0;
+#pragma unroll
+      for (int k = 0; k < 7; ++k) n += vb[r][c + k];
+      hv[r][c] = (unsigned char)n;
+    }
     double s[5] = {0, 0, 0, 0, 0};
 #pragma unroll
     for (int k = 0; k < 7; ++k) {
@@ -134,14 +160,23 @@ __global__ __launch_bounds__(256) void psnr_ssim_tile_kernel(const float* __rest
   }
   __syncthreads();
   double ssum = 0.0, esum = 0.0;
+  int n0 = 0, n3 = 0;
   for (int e = tid; e < MT * MT; e += 256) {
     const int r = e / MT, c = e - r * MT;
     const int gy = y0 + r, gx = x0 + c;
-    if (gy < H && gx < W) {
+    bool in0 = gy < H && gx < W, in3 = gy >= 3 && gy < H - 3 && gx >= 3 && gx < W - 3;
+    if constexpr (MASKED) {
+      int n = 0;
+#pragma unroll
+      for (int k = 0; k < 7; ++k) n += hv[r + k][c];
+      in0 = vb[r + 3][c + 3] != 0; in3 = n == 49;     // (both imply the unmasked conditions: vb is 0 outside the image)
+      n0 += in0; n3 += in3;
+    }
+    if (in0) {
       const float d = a[r + 3][c + 3] - b[r + 3][c + 3];   // skimage: float32 difference, squared, float64 mean
       esum += (double)(d * d);
     }
-    if (gy >= 3 && gy < H - 3 && gx >= 3 && gx < W - 3) {
+    if (in3) {
       double s[5] = {0, 0, 0, 0, 0};
 #pragma unroll
       for (int k = 0; k < 7; ++k)
@@ -158,38 +193,75 @@ __global__ __launch_bounds__(256) void psnr_ssim_tile_kernel(const float* __rest
     }
   }
   red[tid][0] = ssum; red[tid][1] = esum;
+  if constexpr (MASKED) { redi[tid][0] = n3; redi[tid][1] = n0; }
   __syncthreads();
   for (int st = 128; st > 0; st >>= 1) {
-    if (tid < st) { red[tid][0] += red[tid + st][0]; red[tid][1] += red[tid + st][1]; }
+    if (tid < st) {
+      red[tid][0] += red[tid + st][0]; red[tid][1] += red[tid + st][1];
+      if constexpr (MASKED) { redi[tid][0] += redi[tid + st][0]; redi[tid][1] += redi[tid + st][1]; }
+    }
     __syncthreads();
   }
   if (tid == 0) {
     const size_t blk = ((size_t)img * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     part[2 * blk] = red[0][0]; part[2 * blk + 1] = red[0][1];
+    if constexpr (MASKED) { pcnt[2 * blk] = redi[0][0]; pcnt[2 * blk + 1] = redi[0][1]; }
   }
 }
 
 // out[0] = mean_i 10*log10(R^2 / mse_i), out[1] = mean_i mean(SSIM map_i over the valid interior)
+// MASKED: an image contributes its PSNR iff it has a valid pixel and its SSIM iff it has an all-valid window; the means are taken
+// over the contributing images (counts2), NaN where there is none.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void psnr_ssim_final_kernel(const double* __restrict__ part, int tiles_per_img, int B,
                                                               int H, int W, const float* __restrict__ mm,
-                                                              float* __restrict__ out) {
+                                                              float* __restrict__ out, const int* __restrict__ pcnt,
+                                                              int* __restrict__ counts2) {
   __shared__ double r1[256], r2[256];
+  __shared__ int c1[MASKED ? 256 : 1], c2[MASKED ? 256 : 1];
   const double R = (double)(mm[513] - mm[512]);
   double ps = 0.0, ss = 0.0;
+  int np = 0, ns = 0;
   for (int img = threadIdx.x; img < B; img += 256) {
     double s = 0.0, e = 0.0;
     for (int k = 0; k < tiles_per_img; ++k) { s += part[2 * ((size_t)img * tiles_per_img + k)]; e += part[2 * ((size_t)img * tiles_per_img + k) + 1]; }
-    const double mse = e / ((double)H * W);
-    ps += 10.0 * log10(R * R / mse);
-    ss += s / ((double)(H - 6) * (W - 6));
+    if constexpr (MASKED) {
+      long long n3 = 0, n0 = 0;
+      for (int k = 0; k < tiles_per_img; ++k) { n3 += pcnt[2 * ((size_t)img * tiles_per_img + k)]; n0 += pcnt[2 * ((size_t)img * tiles_per_img + k) + 1]; }
+      if (n0 > 0) {
+        const double mse = e / (double)n0;
+        ps += 10.0 * log10(R * R / mse);
+        ++np;
+      }
+      if (n3 > 0) {
+        ss += s / (double)n3;
+        ++ns;
+      }
+    } else {
+      const double mse = e / ((double)H * W);
+      ps += 10.0 * log10(R * R / mse);
+      ss += s / ((double)(H - 6) * (W - 6));
+    }
   }
   r1[threadIdx.x] = ps; r2[threadIdx.x] = ss;
+  if constexpr (MASKED) { c1[threadIdx.x] = np; c2[threadIdx.x] = ns; }
   __syncthreads();
   for (int st = 128; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st) { r1[threadIdx.x] += r1[threadIdx.x + st]; r2[threadIdx.x] += r2[threadIdx.x + st]; }
+    if ((int)threadIdx.x < st) {
+      r1[threadIdx.x] += r1[threadIdx.x + st]; r2[threadIdx.x] += r2[threadIdx.x + st];
+      if constexpr (MASKED) { c1[threadIdx.x] += c1[threadIdx.x + st]; c2[threadIdx.x] += c2[threadIdx.x + st]; }
+    }
     __syncthreads();
   }
-  if (threadIdx.x == 0) { out[0] = (float)(r1[0] / B); out[1] = (float)(r2[0] / B); }
+  if (threadIdx.x == 0) {
+    if constexpr (MASKED) {
+      out[0] = c1[0] > 0 ? (float)(r1[0] / c1[0]) : __uint_as_float(0x7FC00000u);
+      out[1] = c2[0] > 0 ? (float)(r2[0] / c2[0]) : __uint_as_float(0x7FC00000u);
+      counts2[0] = c1[0]; counts2[1] = c2[0];
+    } else {
+      out[0] = (float)(r1[0] / B); out[1] = (float)(r2[0] / B);
+    }
+  }
 }
 
 }  // namespace
@@ -230,10 +302,40 @@ int launch_psnr_ssim(const float* pred, const float* targ, int B, int H, int W, 
   if (mmb > 256) mmb = 256;
   if (mmb < 1) mmb = 1;
   const dim3 grid((W + MT - 1) / MT, (H + MT - 1) / MT, B);
-  hipLaunchKernelGGL(minmax_partial_kernel, dim3(mmb), dim3(256), 0, s, targ, n, mm);
+  hipLaunchKernelGGL(minmax_partial_kernel<false>, dim3(mmb), dim3(256), 0, s, targ, n, mm, (const unsigned char*)nullptr, H, W, 1);
   hipLaunchKernelGGL(minmax_final_kernel, dim3(1), dim3(64), 0, s, mm, mmb);
-  hipLaunchKernelGGL(psnr_ssim_tile_kernel, grid, dim3(256), 0, s, pred, targ, mm, H, W, part);
-  hipLaunchKernelGGL(psnr_ssim_final_kernel, dim3(1), dim3(256), 0, s, part, (int)(grid.x * grid.y), B, H, W, mm, out2);
+  hipLaunchKernelGGL(psnr_ssim_tile_kernel<false>, grid, dim3(256), 0, s, pred, targ, mm, H, W, part,
+                     (const unsigned char*)nullptr, 1, (int*)nullptr);
+  hipLaunchKernelGGL(psnr_ssim_final_kernel<false>, dim3(1), dim3(256), 0, s, part, (int)(grid.x * grid.y), B, H, W, mm, out2,
+                     (const int*)nullptr, (int*)nullptr);
+  SIFSR_LAUNCH_CHECK();
+  return SIFSR_OK;
+}
+
+// scratch: the unmasked layout [528 floats: min / max partials][per-tile double pairs], then the per-tile count pairs
+size_t psnr_ssim_masked_scratch_bytes(int B, int H, int W) {
+  const size_t tiles = (size_t)((W + MT - 1) / MT) * ((H + MT - 1) / MT);
+  return 528 * sizeof(float) + (size_t)B * tiles * 2 * sizeof(double) + (size_t)B * tiles * 2 * sizeof(int) + 64;
+}
+
+int launch_psnr_ssim_masked(const float* pred, const float* targ, const unsigned char* valid, int scale, int B, int H, int W,
+                            void* scratch, float* out2, int* counts2, hipStream_t s) {
+  if (B < 1 || B > 65535 || H < 7 || W < 7 || (long long)H * W >= (1LL << 31) || (H + MT - 1) / MT > 65535) return SIFSR_ERR_SHAPE;
+  if ((scale != 1 && scale != 4) || H % scale || W % scale) return SIFSR_ERR_SHAPE;
+  const dim3 grid((W + MT - 1) / MT, (H + MT - 1) / MT, B);
+  const size_t tiles = (size_t)grid.x * grid.y;
+  float* mm = reinterpret_cast<float*>(scratch);
+  double* part = reinterpret_cast<double*>(reinterpret_cast<char*>(scratch) + 528 * sizeof(float));
+  int* pcnt = reinterpret_cast<int*>(part + (size_t)B * tiles * 2);
+  const size_t n = (size_t)B * H * W;
+  int mmb = (int)((n + 256 * 64 - 1) / (256 * 64));
+  if (mmb > 256) mmb = 256;
+  if (mmb < 1) mmb = 1;
+  hipLaunchKernelGGL(minmax_partial_kernel<true>, dim3(mmb), dim3(256), 0, s, targ, n, mm, valid, H, W, scale);
+  hipLaunchKernelGGL(minmax_final_kernel, dim3(1), dim3(64), 0, s, mm, mmb);
+  hipLaunchKernelGGL(psnr_ssim_tile_kernel<true>, grid, dim3(256), 0, s, pred, targ, (const float*)mm, H, W, part, valid, scale, pcnt);
+  hipLaunchKernelGGL(psnr_ssim_final_kernel<true>, dim3(1), dim3(256), 0, s, (const double*)part, (int)tiles, B, H, W,
+                     (const float*)mm, out2, (const int*)pcnt, counts2);
   SIFSR_LAUNCH_CHECK();
   return SIFSR_OK;
 }

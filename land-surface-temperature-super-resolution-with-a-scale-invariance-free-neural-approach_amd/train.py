@@ -10,7 +10,10 @@ Partly valid patches: with ``valid`` (b,1,w,w) and ``n_valid`
 ``MinedDataset(masked=True)``), and a gap pixel contributes nothing to the loss or the gradient.  Two things are NOT gap-aware and
 stay what they are: PSNR / SSIM of an epoch are scored against the filled ``lst_up`` over all pixels, and under data-parallel
 runs each rank normalises its loss by its OWN ``n_valid`` before the gradients are averaged (as BatchNorm uses per-replica
-statistics), so ranks with few valid pixels weigh their pixels more.
+statistics), so ranks with few valid pixels weigh their pixels more.  ``masked_metrics=True`` makes the first
+gap-aware: ``train_epoch`` / ``eval_epoch`` / ``fit`` then score a batch of five with ``metrics.masked_psnr_ssim(sr, lst_up, valid)``
+-- PSNR over the valid pixels, SSIM over the all-valid 7x7 windows -- and average over the batches that have such pixels; the
+default keeps the numbers above.
 """
 from __future__ import annotations
 
@@ -119,14 +122,37 @@ class ModelCheckpoint:
             self.train_state = "continue"
 
 
-def train_epoch(model, loader, optimizer, stats, alpha, gamma, kind="sr2", device="cuda", with_metrics=True):
+def _score(sr, lst_up, valid, masked_metrics, acc, den):
+    """PSNR / SSIM of one batch into acc[3:5], the number of batches they are means of into den[3:5]; nothing is read back."""
+    if masked_metrics and valid is not None:
+        m = torch.stack(_metrics.masked_psnr_ssim(sr, lst_up, valid)).double()
+        ok = ~torch.isnan(m)                              # no valid pixel / no all-valid window in the whole batch
+        acc[3:] += torch.where(ok, m, torch.zeros_like(m))
+        den[3:] += ok
+    else:
+        ps, ss = _metrics.psnr_ssim(sr, lst_up)
+        acc[3] += ps; acc[4] += ss
+        den[3:] += 1
+
+
+def _epoch_means(acc, den, n, with_metrics):
+    den[:3] = max(n, 1)
+    if not with_metrics or n == 0:
+        den[3:] = max(n, 1)
+    return tuple((acc / den).tolist())
+
+
+def train_epoch(model, loader, optimizer, stats, alpha, gamma, kind="sr2", device="cuda", with_metrics=True,
+                masked_metrics=False):
     """The reference's ``train_step`` over a DataLoader (train_model_B_gradFTM.py:84-138): per batch ``.to(device)`` x3
     (:89) and one optimisation step; returns the epoch means (ds_loss, percep_loss, loss, psnr, ssim), PSNR / SSIM of
     the training-mode prediction against ``lst_up`` as the reference scores them (:126-127) but on the device
     (``metrics.psnr_ssim``).  The per-batch scalars stay on the device and are read back ONCE per
     epoch; the reference calls ``.item()`` three times and copies two full tensors to the host per batch.
-    Batches of five (masked loaders / datasets) take the masked step; their PSNR / SSIM are not gap-aware (module docstring)."""
+    Batches of five (masked loaders / datasets) take the masked step; their PSNR / SSIM are not gap-aware unless
+    ``masked_metrics`` (module docstring)."""
     acc = torch.zeros(5, dtype=torch.float64, device=device)
+    den = torch.zeros(5, dtype=torch.float64, device=device)
     n = 0
     for batch in loader:
         lst, lst_up, ndvi, valid, n_valid = _unpack_batch(batch, device)
@@ -134,18 +160,19 @@ def train_epoch(model, loader, optimizer, stats, alpha, gamma, kind="sr2", devic
                                       valid=valid, n_valid=n_valid)
         acc[0] += ds.detach(); acc[1] += pl.detach(); acc[2] += loss.detach()
         if with_metrics:
-            ps, ss = _metrics.psnr_ssim(sr, lst_up)
-            acc[3] += ps; acc[4] += ss
+            _score(sr, lst_up, valid, masked_metrics, acc, den)
         n += 1
-    return tuple((acc / max(n, 1)).tolist())
+    return _epoch_means(acc, den, n, with_metrics)
 
 
 @torch.inference_mode()
-def eval_epoch(model, loader, stats, alpha, gamma, kind="sr2", device="cuda", with_metrics=True):
+def eval_epoch(model, loader, stats, alpha, gamma, kind="sr2", device="cuda", with_metrics=True, masked_metrics=False):
     """The reference's ``test_step`` (train_model_B_gradFTM.py:141-237): eval mode, no gradient; epoch means of
-    (ds_loss, percep_loss, loss, psnr, ssim).  Batches of five: the masked loss, as in ``train_epoch``."""
+    (ds_loss, percep_loss, loss, psnr, ssim).  Batches of five: the masked loss and, with ``masked_metrics``, the masked
+    PSNR / SSIM, as in ``train_epoch``."""
     model.eval()
     acc = torch.zeros(5, dtype=torch.float64, device=device)
+    den = torch.zeros(5, dtype=torch.float64, device=device)
     n = 0
     for batch in loader:
         lst, lst_up, ndvi, valid, n_valid = _unpack_batch(batch, device)
@@ -156,19 +183,19 @@ def eval_epoch(model, loader, stats, alpha, gamma, kind="sr2", device="cuda", wi
             ds, pl, loss = masked_sif_loss(kind, sr, lst, valid, n_valid, ndvi, stats["mean_lst"], stats["std_lst"], alpha, gamma)
         acc[0] += ds; acc[1] += pl; acc[2] += loss
         if with_metrics:
-            ps, ss = _metrics.psnr_ssim(sr, lst_up)
-            acc[3] += ps; acc[4] += ss
+            _score(sr, lst_up, valid, masked_metrics, acc, den)
         n += 1
-    return tuple((acc / max(n, 1)).tolist())
+    return _epoch_means(acc, den, n, with_metrics)
 
 
 def fit(model, train_dataset, val_dataset, n_epochs, batch_size, optimizer, alpha, gamma, kind="sr2", device="cuda",
-        checkpoint=None, shuffle=True, generator=None):
+        checkpoint=None, shuffle=True, generator=None, masked_metrics=False):
     """The reference's ``train()`` (train_model_B_gradFTM.py:240-354): two shuffled DataLoaders (:295-296), per epoch
     one training and one validation pass, the same ``metrics`` dict (``train_loss, train_dsloss, train_perceploss,
     train_psnr, train_ssim, val_*``, ``best_epoch``) and early stopping through ``checkpoint`` (``ModelCheckpoint`` or
     the reference's own ``us.model_checkpoint`` object) with restore of the best state (:338-352).  The normalisation
-    statistics come from ``train_dataset.stats`` as in the reference's step (:99-100).  Returns (model, metrics)."""
+    statistics come from ``train_dataset.stats`` as in the reference's step (:99-100).  ``masked_metrics``: as in ``train_epoch``
+    (datasets built with ``masked=True``).  Returns (model, metrics)."""
     from torch.utils.data import DataLoader
     tl = DataLoader(train_dataset, batch_size=batch_size, shuffle=shuffle, generator=generator)
     vl = DataLoader(val_dataset, batch_size=batch_size, shuffle=shuffle, generator=generator)
@@ -176,9 +203,9 @@ def fit(model, train_dataset, val_dataset, n_epochs, batch_size, optimizer, alph
     keys = ("dsloss", "perceploss", "loss", "psnr", "ssim")
     metrics = {f"{split}_{k}": [] for split in ("train", "val") for k in keys}
     for epoch in range(1, n_epochs + 1):
-        for k, v in zip(keys, train_epoch(model, tl, optimizer, stats, alpha, gamma, kind, device)):
+        for k, v in zip(keys, train_epoch(model, tl, optimizer, stats, alpha, gamma, kind, device, masked_metrics=masked_metrics)):
             metrics[f"train_{k}"].append(v)
-        for k, v in zip(keys, eval_epoch(model, vl, stats, alpha, gamma, kind, device)):
+        for k, v in zip(keys, eval_epoch(model, vl, stats, alpha, gamma, kind, device, masked_metrics=masked_metrics)):
             metrics[f"val_{k}"].append(v)
         if checkpoint is not None:
             checkpoint.test_update(model, metrics, "val_loss", epoch)
