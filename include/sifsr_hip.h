@@ -308,7 +308,7 @@ SIFSR_API size_t sifsr_psnr_ssim_scratch_bytes(int B, int H, int W);
 SIFSR_API int sifsr_psnr_ssim(const float* pred, const float* targ, int B, int H, int W, void* scratch, size_t scratch_bytes,
                               float* out2, void* stream);
 
-/* Per-pair ASTER evaluation metrics: the table of model_perf_aster_formatds.py:371-437 without LPIPS, for
+/* Per-pair ASTER evaluation metrics: the table of model_perf_aster_formatds.py:371-437 without LPIPS (that column: sifsr_lpips.h), for
  * B pairs of (B,1,H,W) images, ref = ASTER (overlap_11, im1), pred = prediction (overlap_22, im2); any H, W >= 16.
  * out8 (device, (B,8) float64) rows follow the column names of :507 without 'LPIPS':
  *   PSNR, SSIM (skimage 0.22 defaults, :430-431), RMSE (:432), RMSE low / mean / high grad (:379-404; g = |ref -

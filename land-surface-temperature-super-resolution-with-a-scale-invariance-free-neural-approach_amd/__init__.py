@@ -20,6 +20,8 @@ Drop-in surface (SURVEY.md §8 b):
                                        valid pixels, a loss and gradient without the gap pixels (include/sifsr_masked.h)
   metrics.masked_aster_metrics / masked_psnr_ssim, train_epoch(masked_metrics=)  <- no counterpart: both metric sets over the valid
                                        pixels of rasters with gaps, a term counted iff its whole stencil is valid (include/sifsr_scores.h)
+  lpips.LPIPS, metrics.aster_table     <- lpips.py:226-292, :351-358, model_perf_aster_formatds.py:134, :405-410: LPIPS-VGG16 on the device
+                                       with weights the caller supplies (nothing is fetched), the table's ninth column (include/sifsr_lpips.h)
   products.decode / PatchMiner / MinedPatches, dataset.MinedDataset  <- process_modis.py:38-335, data_preparation.py:32-102
                                        (raw granule arrays -> patches + statistics.json, on device)
 
@@ -30,7 +32,7 @@ and registers ``sifsr`` / ``sifsr.<submodule>`` as aliases of the same module ob
 import importlib
 import sys
 
-_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "gaps", "predict", "baselines", "products")
+_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "gaps", "predict", "baselines", "products", "lpips")
 for _m in _SUBMODULES:
     importlib.import_module(__name__ + "." + _m)
 

@@ -47,7 +47,7 @@ def ssim_skimage(predictions, targets):
 
 
 # ---- per-pair ASTER evaluation table, model_perf_aster_formatds.py:371-437 ----------------------------
-# The column names of :507 without 'LPIPS' (out of scope: lpips.py fetches its weights from URLs).
+# The column names of :507 without 'LPIPS' (that column: aster_table / METRIC_NAMES_WITH_LPIPS below, sifsr.lpips).
 METRIC_NAMES = ("PSNR", "SSIM", "RMSE", "RMSE (low grad per image)", "RMSE (mean grad per image)",
                 "RMSE (high grad per image)", "GSSIM", "RMSE_grad")
 
@@ -124,6 +124,25 @@ def gradient_strata(reference):
     _lib.call("sifsr_gradient_strata", reference.detach(), B, H, W, _taps_c(0.1, 4, None), g, q, counts,
               _lib.stream_ptr(reference.device))
     return g, q[:, 0], q[:, 1], counts
+
+
+# ---- the nine-column table (include/sifsr_lpips.h) ------------------------------------------------------------
+# The column names of model_perf_aster_formatds.py:507, in its order.
+METRIC_NAMES_WITH_LPIPS = METRIC_NAMES[:7] + ("LPIPS",) + METRIC_NAMES[7:]
+
+
+def aster_table(reference, prediction, lpips, data_range=None):
+    """The reference's per-pair table with all nine columns ``METRIC_NAMES_WITH_LPIPS`` -> (B,9) float64 device tensor.
+
+    ``lpips``: a ``sifsr.lpips.LPIPS`` (it carries the weights the caller supplied); the column is its ``pairs`` path, the pair
+    min/max-normalised to [0, 1] and repeated to three channels (model_perf_aster_formatds.py:373-374, :405-410).  The other eight
+    columns are ``aster_metrics(reference, prediction, data_range)`` bit for bit; tensors or lists as it takes them."""
+    rows = aster_metrics(reference, prediction, data_range)
+    if isinstance(reference, (list, tuple)):
+        lp = lpips.pairs(list(reference), list(prediction))
+    else:
+        lp = lpips.pairs(reference, prediction)
+    return torch.cat((rows[:, :7], lp[:, 5:6], rows[:, 7:]), dim=1)
 
 
 # ---- scoring rasters with gaps (DESIGN.md §9 f10, include/sifsr_scores.h) ------------------------------------------------------
