@@ -22,6 +22,9 @@ Drop-in surface (SURVEY.md §8 b):
                                        pixels of rasters with gaps, a term counted iff its whole stencil is valid (include/sifsr_scores.h)
   lpips.LPIPS, metrics.aster_table     <- lpips.py:226-292, :351-358, model_perf_aster_formatds.py:134, :405-410: LPIPS-VGG16 on the device
                                        with weights the caller supplies (nothing is fetched), the table's ninth column (include/sifsr_lpips.h)
+  conserve.consistency / conserve, predict_granule(conserve=) / predict_granule_gaps(conserve=) / GranulePredictor(conserve=)  <- no
+                                       counterpart for the network (TsHARP's correction_linreg, utils.py:897, is the baselines' form):
+                                       the residual LST - D(SR) over the valid cells and its correction (include/sifsr_conserve.h)
   products.decode / PatchMiner / MinedPatches, dataset.MinedDataset  <- process_modis.py:38-335, data_preparation.py:32-102
                                        (raw granule arrays -> patches + statistics.json, on device)
 
@@ -32,7 +35,7 @@ and registers ``sifsr`` / ``sifsr.<submodule>`` as aliases of the same module ob
 import importlib
 import sys
 
-_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "gaps", "predict", "baselines", "products", "lpips")
+_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "gaps", "conserve", "predict", "baselines", "products", "lpips")
 for _m in _SUBMODULES:
     importlib.import_module(__name__ + "." + _m)
 

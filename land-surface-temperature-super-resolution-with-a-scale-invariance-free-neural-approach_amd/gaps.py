@@ -20,6 +20,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib, pipeline
+from .conserve import granule_option
 
 
 def _valid_raster(valid, shape, device, what="valid"):
@@ -101,6 +102,7 @@ def blend_active_tiles(sr, slot, valid, window, stats, overlap=0, cover_edges=Fa
     return out
 
 
+@granule_option
 @torch.inference_mode()
 def predict_granule_gaps(model, lst_g, ndvi_g, stats, mask=None, window=64, batch=256, overlap=16, cover_edges=True,
                          fill_value=float("nan"), return_info=False):
@@ -113,7 +115,13 @@ def predict_granule_gaps(model, lst_g, ndvi_g, stats, mask=None, window=64, batc
     host synchronisation.  At valid pixels the result is bit-identical to ``predict_granule`` on the filled raster with the same
     layout; nothing is valid: the all-``fill_value`` raster, no forward.
 
-    ``return_info``: also {"valid": bool (h,w) device tensor, "n_active": int, "n_tiles": int}."""
+    Keyword-only ``conserve=k`` (``conserve.granule_option``): k residual-correction steps on the blended raster
+    (``conserve.conserve`` with the same ``mask``: only cells whose LST pixel is valid move, and the correction fades out towards
+    a gap); 0, the default, runs none.
+
+    ``return_info``: also {"valid": bool (h,w) device tensor, "n_active": int, "n_tiles": int} and, with ``conserve`` > 0,
+    "conserve_stats": the float64 device tensor (conserve+1, 4) of (count, bias, RMSE, max |r|) before the first step and after
+    every step."""
     _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
     if lst_g.dim() != 2:
         raise _lib.SifsrError(f"lst granule: expected a 2-D raster, got {tuple(lst_g.shape)}")

@@ -6,11 +6,15 @@ through the network in large batches (config 4 of BASELINE.json: batch 256).  ``
 tiles with an overlap and a last tile flush to each edge and blend them (a seamless, complete raster; not in the reference).  HDF/GeoTIFF I/O is out
 of scope; inputs are the already normalised ``lst_up`` / ``ndvi`` tiles.  ``predict_granule_gaps`` (sifsr/gaps.py)
 is ``predict_granule`` for granules with cloud / ocean / fill pixels: gaps filled, all-gap tiles skipped, the output masked.
+``conserve=k`` on the granule calls adds k residual-correction steps after the blend (sifsr/conserve.py): the
+output, seen through the sensor's MTF and decimated by 4, then returns the LST raster it was predicted from; 0, the default,
+leaves every bit as it was.
 """
 from __future__ import annotations
 
 import torch
 
+from .conserve import granule_option
 from .gaps import fill_gaps, predict_granule_gaps, select_tiles  # noqa: F401  (the gap-aware path, DESIGN.md §9 f8)
 
 
@@ -25,11 +29,15 @@ def predict_tiles(model, lst_up, ndvi, stats, batch=256):
     return out
 
 
-def _granule_forward(model, lst_g, ndvi_g, stats, window, batch, overlap, cover_edges, x=None, sr=None, out=None):
+def _granule_forward(model, lst_g, ndvi_g, stats, window, batch, overlap, cover_edges, x=None, sr=None, out=None, conserve=0):
     """prepare -> batched eval forwards -> blend, all enqueued on the current stream.  x / sr / out: static buffers of a
     captured run (x and sr hold a whole number of batches: the tiles past the last real one are zeros and their predictions
-    are never read); None: allocated here and the last batch is as short as it is."""
-    from . import pipeline
+    are never read); None: allocated here and the last batch is as short as it is.  conserve: that many correction steps on the
+    blended raster, in place, on the same stream (``conserve.conserve``; its scratch is allocated here, in a captured run from the
+    graph's own pool)."""
+    from . import conserve as _conserve, pipeline
+    if int(conserve) < 0:
+        raise pipeline._lib.SifsrError(f"conserve must be a step count >= 0, got {conserve}")
     h, w = lst_g.shape
     if x is None:
         x, _ = pipeline.granule_to_tiles(lst_g, ndvi_g, stats, window=window, clip_ndvi=True, overlap=overlap,
@@ -41,9 +49,13 @@ def _granule_forward(model, lst_g, ndvi_g, stats, window, batch, overlap, cover_
                                       cover_edges=cover_edges, out=x)[0].shape[0]
     for i in range(0, x.shape[0], batch):
         sr[i:i + batch] = model(x[i:i + batch])
-    return pipeline.blend_tiles(sr[:n], (h, w), window, stats, overlap, cover_edges, out=out)
+    out = pipeline.blend_tiles(sr[:n], (h, w), window, stats, overlap, cover_edges, out=out)
+    if int(conserve) > 0:
+        _conserve.conserve(out, lst_g, None, n_iter=int(conserve), out=out)
+    return out
 
 
+@granule_option
 @torch.inference_mode()
 def predict_granule(model, lst_g, ndvi_g, stats, window=64, batch=256, overlap=0, cover_edges=False):
     """The whole block loop of predict.py:84-103 on the device: raw LST raster (h,w) [K] + raw NDVI raster
@@ -53,7 +65,10 @@ def predict_granule(model, lst_g, ndvi_g, stats, window=64, batch=256, overlap=0
 
     ``overlap`` (LST pixels, 0..window/2) lays the tiles at stride ``window - overlap`` and merges their predictions with a
     normalised feathered blend, which removes the seams between independently predicted tiles; ``cover_edges`` adds a last
-    tile flush to the bottom / right edge so that no pixel stays 0.  Both default to the reference's behaviour."""
+    tile flush to the bottom / right edge so that no pixel stays 0.  Both default to the reference's behaviour.
+
+    Keyword-only ``conserve=k`` (``conserve.granule_option``): k steps of ``conserve.conserve`` on the blended raster (cells of
+    0 K / non-finite LST pixels and the pixels no tile reached keep their bits); 0, the default: none."""
     model.eval()
     return _granule_forward(model, lst_g, ndvi_g, stats, window, batch, overlap, cover_edges)
 
@@ -113,15 +128,19 @@ class GranulePredictor:
     stream, replayed per granule.  All buffers are static; the tiles are padded with zero tiles to a whole number of batches
     (every forward has the captured batch shape; the padding's predictions are not read).  ``__call__(lst_g, ndvi_g)`` copies
     the rasters in, replays and returns a clone of the output raster -- bit-identical to the eager ``predict_granule`` with the
-    same arguments.  There is no captured form of ``predict_granule_gaps``: a graph cannot have a data-dependent batch count."""
+    same arguments; ``conserve`` steps are part of the captured chain.  There is no captured form of ``predict_granule_gaps``: a
+    graph cannot have a data-dependent batch count."""
 
-    def __init__(self, model, lst_shape, stats, window=64, overlap=0, cover_edges=False, batch=256, device=None):
+    def __init__(self, model, lst_shape, stats, window=64, overlap=0, cover_edges=False, batch=256, device=None, conserve=0):
         from . import pipeline
         self.model = model.eval()
         dev = device or next(model.parameters()).device
         h, w = (int(v) for v in lst_shape)
         self.lst_shape, self.stats, self.window = (h, w), stats, int(window)
         self.overlap, self.cover_edges, self.batch = int(overlap), bool(cover_edges), int(batch)
+        self.conserve = int(conserve)
+        if self.conserve < 0:
+            raise pipeline._lib.SifsrError(f"conserve must be a step count >= 0, got {conserve}")
         if self.overlap or self.cover_edges:
             ty, tx = pipeline._mosaic_tiles((h, w), (4 * h, 4 * w), self.window, self.overlap, self.cover_edges)
         else:
@@ -151,7 +170,7 @@ class GranulePredictor:
 
     def _run(self):
         _granule_forward(self.model, self.lst, self.ndvi, self.stats, self.window, self.batch, self.overlap, self.cover_edges,
-                         x=self.x, sr=self.sr, out=self.out)
+                         x=self.x, sr=self.sr, out=self.out, conserve=self.conserve)
 
     @torch.inference_mode()
     def __call__(self, lst_g, ndvi_g):
