@@ -12,8 +12,10 @@ training scripts use, the hot-path ones on MI355X:
                                                                              (A = -0.75, half-pixel centres, edge clamp)
   us.TsHARP, us.ATPRK, us.AATPRK                   utils.py:1213-1253, :1588-1606 -> device kernels + host variogram fit
                                                                              (sifsr.baselines); 2-D numpy in, float64 numpy out
+  us.DMS                                           data_mining_sharpener_modified.py as model_perf_aster_formatds.py:220-250
+                                                                             calls it -> device kernels (sifsr.baselines.dms)
 
-GeoTIFF / HDF I/O, the DMS sharpener and the plotting helpers (GDAL, OpenCV, rasterio: not installed, out of scope --
+GeoTIFF / HDF I/O, the file interface of the DMS sharpener and the plotting helpers (GDAL, OpenCV, rasterio: not installed, out of scope --
 SURVEY.md §2) raise ``NotImplementedError`` naming what was asked for.
 """
 import json
@@ -120,6 +122,22 @@ def AATPRK(temp_coarse, index_coarse, index_fine, scale, scc, b_radius=2, block_
                             min_T=min_T)[0, 0].cpu().numpy().astype(np.float64)
 
 
+def DMS(temp_coarse, index_fine, scale, n_estimators=10, seed=0):
+    """The DMS sharpener on arrays instead of GeoTIFF files: global NDVI -> LST bagged trees with per-leaf ridge regression and
+    the T^4 residual correction -> (4h,4w) float64 numpy.  Deterministic for a given ``seed`` (the reference's is not)."""
+    from sifsr import baselines
+    if scale != 4:
+        raise NotImplementedError(f"DMS: only scale=4 (the paper's 1 km -> 250 m) has a gfx950 kernel, got scale={scale}")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    args = []
+    for what, a in (("temp_coarse", temp_coarse), ("index_fine", index_fine)):
+        a = np.asarray(a)
+        if a.ndim != 2:
+            raise ValueError(f"DMS: {what} must be a 2-D array, got shape {a.shape}")
+        args.append(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)[None, None])
+    return baselines.dms(*args, n_estimators=n_estimators, seed=seed)[0, 0].cpu().numpy().astype(np.float64)
+
+
 def _read(file, keys):
     with open(file) as f:
         data = json.load(f)
@@ -162,5 +180,5 @@ def __getattr__(name):
     if name.startswith("__"):
         raise AttributeError(name)
     raise OutOfScopeAttribute(
-        f"utils.{name}: not part of the SIF-CNN-SR hot path (GDAL / OpenCV / rasterio I/O, the DMS sharpener and plots "
+        f"utils.{name}: not part of the SIF-CNN-SR hot path (GDAL / OpenCV / rasterio I/O, the file interface of DMS and plots "
         "are out of scope of the MI355X build, SURVEY.md §2); use the reference's own utils.py for it")

@@ -1,7 +1,8 @@
-"""The classical sharpening baselines the paper compares the network with, on the device (DESIGN.md §9 f6):
+"""The classical sharpening baselines the paper compares the network with, on the device (DESIGN.md §9 f6, f13):
 
     us.TsHARP / us.ATPRK / us.AATPRK                                      utils.py:1213-1253, :1588-1606
     scored per (lst 64x64, ndvi_down 64x64, ndvi 256x256) triple           model_perf_aster_formatds.py:205-218
+    DMS (`dms`, `dms_model`, `dms_apply`; the end of this file)            data_mining_sharpener_modified.py, :220-250
 
 The data-sized parts -- the NDVI/LST regressions, the coarse residual, the empirical semivariogram and the fused unmix +
 correction pass over the fine raster -- are hand-written HIP kernels in float64 (include/sifsr_baselines.h, csrc/baselines.hip);
@@ -251,3 +252,153 @@ def aatprk(lst, ndvi_coarse, ndvi_fine, scc=926.0, b_radius=2, sill=7.0, ran=100
     _lib.call("sifsrb_linfit_window", lst, ndvi_coarse, fit, coef, B, h, w, int(b_radius), float(min_T), s)
     return _kriging(lst, ndvi_coarse, ndvi_fine, coef, True, 2, B, h, w, float(scc), float(sill), float(ran), variogram,
                     return_variogram, s)
+
+
+# ---- DMS, the Data Mining Sharpener (include/sifsr_dms.h, csrc/dms.hip) -----------------------------------
+DMS_MAX_LEAVES, DMS_MIN_TRAIN = 30, 10
+
+
+def _check_dms(lst, ndvi_fine):
+    for t, what in ((lst, "lst"), (ndvi_fine, "ndvi_fine")):
+        if not isinstance(t, torch.Tensor):
+            raise _lib.SifsrError(f"{what} must be a device tensor, got {type(t).__name__}")
+        _lib.require_gpu(t, what)
+        if what == "ndvi_fine" and t.dim() == 4 and t.shape[1] > 1:
+            raise NotImplementedError(f"dms: only one predictor (NDVI) is built, got {t.shape[1]} channels")
+        if t.dim() != 4 or t.shape[1] != 1:
+            raise ValueError(f"{what}: expected (B,1,H,W), got {tuple(t.shape)}")
+    B, _, h, w = lst.shape
+    if tuple(ndvi_fine.shape) != (B, 1, 4 * h, 4 * w):
+        raise ValueError(f"ndvi_fine must be exactly 4x the coarse shape ({B}, 1, {4 * h}, {4 * w}), got {tuple(ndvi_fine.shape)}")
+    if B < 1 or h < 1 or w < 1:
+        raise ValueError(f"empty input {tuple(lst.shape)}")
+    return B, h, w
+
+
+def dms_aggregate(fine, pow4=False):
+    """Stage 1: (B,1,4h,4w) float32 -> (mean, std) (B,h,w) float64, NaN-ignoring, of the 4 x 4 blocks (of fine^4 when pow4)."""
+    _lib.require_gpu(fine, "fine")
+    B, _, H, W = fine.shape
+    if H % 4 or W % 4:
+        raise ValueError(f"the fine raster must be a multiple of 4 on both axes, got {H} x {W}")
+    mean, std = _f64((B, H // 4, W // 4), fine), _f64((B, H // 4, W // 4), fine)
+    _lib.call("sifsrd_aggregate", fine, mean, std, B, H // 4, W // 4, int(bool(pow4)), _lib.stream_ptr(fine.device))
+    return mean, std
+
+
+def dms_training_set(lst, ndvi_fine):
+    """Stages 1 and 2 -> dict(x, cv, weight (B,N) float64, good (B,N) bool, threshold (B,) float64, n_train (B,) int32: 0 where
+    fewer than 10 cells are good).  The percentile's sort is torch.sort."""
+    B, h, w = _check_dms(lst, ndvi_fine)
+    N, s, dev = h * w, _lib.stream_ptr(lst.device), lst.device
+    mean, std = dms_aggregate(ndvi_fine)
+    x, cv = _f64((B, N), lst), _f64((B, N), lst)
+    good = torch.empty((B, N), dtype=torch.uint8, device=dev)
+    _lib.call("sifsrd_trainset", lst, mean, std, x, cv, good, B, h, w, s)
+    good = good.bool()
+    n = good.sum(1)
+    n_train = torch.where(n >= DMS_MIN_TRAIN, n, torch.zeros_like(n))
+    good = good & (n_train > 0)[:, None]
+    inf = torch.full((), float("inf"), dtype=torch.float64, device=dev)
+    srt = torch.sort(torch.where(good, cv, inf), dim=1).values
+    last = (n_train - 1).clamp(min=0)
+    v = last.double() * (80 / 100)                                      # np.percentile(., 80), linear
+    lo = v.floor().long()
+    hi = torch.minimum(lo + 1, last)
+    t = v - lo.double()
+    a, b = srt.gather(1, lo[:, None])[:, 0], srt.gather(1, hi[:, None])[:, 0]
+    thr = torch.where(t >= 0.5, b - (b - a) * (1 - t), a + (b - a) * t)
+    stats = torch.stack([thr, srt[:, 0], srt.gather(1, last[:, None])[:, 0]], 1).contiguous()
+    weight = _f64((B, N), lst)
+    _lib.call("sifsrd_weights", cv, good.to(torch.uint8), stats, weight, B, N, s)
+    return dict(x=x, cv=cv, weight=weight, good=good, threshold=thr, n_train=n_train.int())
+
+
+def _bootstrap_counts(good, n_train, E, seed):
+    """(B,E,N) int32 multiplicities in row-major cell order: per image n_train draws with replacement among its good cells.  The
+    same E x N integers serve every image (scaled to its n_train), so an image's draw does not depend on the batch around it."""
+    B, N = good.shape
+    g = torch.Generator(device=good.device)
+    g.manual_seed(int(seed))
+    r = torch.randint(0, 1 << 31, (E, N), generator=g, device=good.device, dtype=torch.int64)
+    nt = n_train.long()[:, None, None]
+    rank = (r[None] * nt) >> 31                                          # uniform in [0, n_train)
+    valid = torch.arange(N, device=good.device)[None, None, :] < nt
+    order = torch.sort((~good).to(torch.uint8), dim=1, stable=True).indices        # the good cells first, row-major
+    cell = order.gather(1, rank.reshape(B, E * N)).reshape(B, E, N)
+    counts = torch.zeros((B, E, N), dtype=torch.int64, device=good.device)
+    counts.scatter_add_(2, cell, valid.expand(B, E, N).long())                          # integer adds: the order does not matter
+    return counts.int()
+
+
+def dms_model(lst, ndvi_fine, *, n_estimators=10, counts=None, seed=0):
+    """Stages 1-3: fit the bagged trees of every image.  -> dict(thresholds (B,E,29) float64 ascending, +inf padded; nleaf (B,E)
+    int32; leaves (B,E,30,4) float64 = coef, intercept, lo, hi; n_train (B,) int32; counts (B,E,h*w) int32)."""
+    B, h, w = _check_dms(lst, ndvi_fine)
+    E, N, s, dev = int(n_estimators), h * w, _lib.stream_ptr(lst.device), lst.device
+    if not 1 <= E <= 32:
+        raise ValueError(f"n_estimators must be in [1, 32], got {n_estimators}")
+    ts = dms_training_set(lst, ndvi_fine)
+    good, n_train = ts["good"], ts["n_train"]
+    if counts is None:
+        counts = _bootstrap_counts(good, n_train, E, seed)
+    else:
+        if not isinstance(counts, torch.Tensor) or not counts.is_cuda:
+            raise _lib.SifsrError("counts must be a device tensor; there is no CPU path")
+        if tuple(counts.shape) != (B, E, N) or counts.dtype.is_floating_point or counts.dtype == torch.bool:
+            raise ValueError(f"counts: expected an integer ({B}, {E}, {N}) tensor, got {tuple(counts.shape)} {counts.dtype}")
+        counts = counts.int()
+    # the samples in ascending order of the float32 feature, the cells that are not good last
+    inf32 = torch.full((), float("inf"), dtype=torch.float32, device=dev)
+    perm = torch.sort(torch.where(good, ts["x"].float(), inf32), dim=1, stable=True).indices
+    xs = ts["x"].gather(1, perm).contiguous()
+    ys = lst.reshape(B, N).double().gather(1, perm).contiguous()
+    ws = ts["weight"].gather(1, perm).contiguous()
+    cs = counts.gather(2, perm[:, None, :].expand(B, E, N)).contiguous()
+    nbytes = _lib.call("sifsrd_fit_scratch_bytes", B, E, N)
+    if nbytes == 0:
+        raise ValueError(f"unsupported shape B={B}, E={E}, N={N}")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    thresholds = _f64((B, E, DMS_MAX_LEAVES - 1), lst)
+    nleaf = torch.empty((B, E), dtype=torch.int32, device=dev)
+    leaves = _f64((B, E, DMS_MAX_LEAVES, 4), lst)
+    _lib.call("sifsrd_fit", xs, ys, ws, cs, n_train, scratch, thresholds, nleaf, leaves, B, E, N, s)
+    return dict(thresholds=thresholds, nleaf=nleaf, leaves=leaves, n_train=n_train, counts=counts)
+
+
+def dms_apply(model, lst, ndvi_fine, correct=True):
+    """Stages 4 and 5: the ensemble's prediction of the fine index and (correct=True) the radiance residual correction against
+    `lst`.  -> (B,1,4h,4w) float32; an image without a model (n_train == 0) is all NaN."""
+    B, h, w = _check_dms(lst, ndvi_fine)
+    s = _lib.stream_ptr(lst.device)
+    thr, nleaf, leaves = model["thresholds"], model["nleaf"], model["leaves"]
+    E = nleaf.shape[1]
+    if tuple(thr.shape) != (B, E, DMS_MAX_LEAVES - 1) or tuple(leaves.shape) != (B, E, DMS_MAX_LEAVES, 4) or nleaf.shape[0] != B:
+        raise ValueError("the model does not belong to this batch")
+    sr = torch.empty((B, 1, 4 * h, 4 * w), dtype=torch.float32, device=lst.device)
+    _lib.call("sifsrd_predict", ndvi_fine, thr.contiguous(), nleaf.contiguous(), leaves.contiguous(), sr, B, E, h, w, s)
+    if not correct:
+        return sr
+    m4 = _f64((B, h, w), lst)
+    _lib.call("sifsrd_aggregate", sr, m4, None, B, h, w, 1, s)
+    out = torch.empty_like(sr)
+    _lib.call("sifsrd_correct", lst, sr, m4, out, B, h, w, s)
+    return out
+
+
+def dms(lst, ndvi_fine, *, n_estimators=10, counts=None, seed=0, correct=True, return_model=False, moving_window_size=0,
+        predictors=1, quality=None):
+    """DMS as the reference's evaluation runs it (model_perf_aster_formatds.py:220-250): NDVI -> LST trees with per-leaf ridge,
+    global regression, T^4 residual correction.  lst (B,1,h,w) float32 Kelvin (NaN or <= 0: no data), ndvi_fine (B,1,4h,4w).
+    `counts`: (B,E,h*w) integer bootstrap multiplicities in row-major cell order; absent, they are drawn on the device from
+    `seed`.  Deterministic: the same inputs and seed give the same bits.  Local windows, several predictors and quality files are
+    the reference's and not built here."""
+    if moving_window_size:
+        raise NotImplementedError("dms: local (moving window) regressions are not built; only movingWindowSize=0")
+    if predictors != 1:
+        raise NotImplementedError("dms: only one predictor (NDVI) is built")
+    if quality is not None:
+        raise NotImplementedError("dms: low-resolution quality files are not built")
+    model = dms_model(lst, ndvi_fine, n_estimators=n_estimators, counts=counts, seed=seed)
+    out = dms_apply(model, lst, ndvi_fine, correct=correct)
+    return (out, model) if return_model else out
