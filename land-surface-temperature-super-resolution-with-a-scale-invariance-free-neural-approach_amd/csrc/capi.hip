@@ -199,8 +199,9 @@ static int conv3x3_dgrad_lowp(int mode, const float* dy, int cout, const float* 
   a.B = B; a.H = H; a.W = W; a.NQ = cout / 16;
   int rc = launch_conv3x3_mfma(a, cin, 1, S(stream));
   if (rc) return rc;
-  // border fold: rounds its operands like the main kernel
-  return launch_dgrad_border_fix(dy, cout, wdgrad, cin, g0, C0, C0, g1 ? g1 : g0, g1 ? C1 : C0, B, H, W, S(stream), mode);
+  // image border: dL/dy is a stored tensor here, so the border pixels are formed whole (operands rounded like the main kernel's)
+  // and rounded once; updating the main kernel's bf16 values with the fold would round them twice
+  return launch_dgrad_border_whole_bf16(dy, cout, wdgrad, cin, g0, C0, C0, g1 ? g1 : g0, g1 ? C1 : C0, addend, B, H, W, S(stream));
 }
 int sifsr_conv3x3_dgrad_bf16(const float* dy, int cout, const float* wdgrad, int cin, float* g0, int C0, float* g1, int C1,
                              const float* addend, int B, int H, int W, void* stream) {

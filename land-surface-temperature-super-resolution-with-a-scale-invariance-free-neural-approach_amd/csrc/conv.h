@@ -151,6 +151,10 @@ int launch_dgrad_border_fix(const float* dy, int Cout, const float* wdg_layer, i
                             int split_ch, float* g1, int C1, int B, int H, int W, hipStream_t s, int bf16 = 0,
                             const float* bn_y = nullptr, const float* bn_scale = nullptr, const float* bn_shift = nullptr,
                             float* bn_partials = nullptr, int masked = 0);   // masked: g0 holds g * [bn_y*scale+shift > 0] (with bn_partials)
+// bf16 storage with dL/dy stored everywhere: the image-border pixels formed whole (all taps + fold + addend) and rounded
+// once, replacing what the main kernel stored there.
+int launch_dgrad_border_whole_bf16(const float* dy, int Cout, const float* wdg_layer, int Cin, float* g0, int C0, int split_ch,
+                                   float* g1, int C1, const float* addend, int B, int H, int W, hipStream_t s);
 int dgrad_border_waves(int B, int H, int W, int Cin);   // rows of bn_partials ([wave][16][2]) the border kernel writes
 
 // wwf / wwd (optional): Winograd-domain packs of all layers, 16/9 of the size and offsets of wfwd

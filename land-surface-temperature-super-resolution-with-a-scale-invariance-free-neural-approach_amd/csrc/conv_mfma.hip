@@ -1010,6 +1010,77 @@ __global__ __launch_bounds__(256, 8) void dgrad_border_kernel(const float* __res
   }
 }
 
+// The image-border pixels of a bf16-stored input gradient in ONE rounding (sifsr_conv3x3_dgrad_bf16).  dgrad_border_kernel
+// above updates what the main kernel stored: on a bf16 tensor that is rn(rn(zero-padded sum + addend) + fold), two roundings
+// (up to 2^-8 (|stored partial| + |result|) instead of 2^-8 |result|).  Where dL/dy is a stored tensor, the border pixel can be
+// formed whole instead: the adjoint of replicate padding is
+//   g[q] = sum_t W_t^T * sum_{p : clamp(p + t) = q} dy[p],
+// and per axis {p : clamp(p + t) = q} = {q - t, if inside} + {q, if (q = 0, t = -1) or (q = N-1, t = +1)} -- the 2-D set is the
+// product, at most four sources per tap.  Same wave map, weight pack and operand rounding as dgrad_border_kernel; fp32
+// accumulation of all nine taps, + addend, one store that replaces the main kernel's value.  (The model's backward cannot use
+// this: there dL/dy exists on the image-border pixels only, ConvArgs::bw_border.)
+__global__ __launch_bounds__(256) void dgrad_border_whole_bf16_kernel(const float* __restrict__ dy, int Cout,
+                                                                      const float* __restrict__ wd, int Cin, float* g0, int C0,
+                                                                      int split_ch, float* g1, int C1,
+                                                                      const float* __restrict__ addend, int B, int H, int W) {
+  const int lane = threadIdx.x & 63;
+  const int wave_g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int NBI = Cin / 16, NQ = Cout / 16;
+  const int seg_tb = (W + 15) / 16, seg_lr = (H - 2 + 15) / 16;
+  const int per_img = (2 * seg_tb + 2 * seg_lr) * NBI;
+  if (wave_g >= B * per_img) return;                       // wave-uniform
+  const int b = wave_g / per_img;
+  int r = wave_g - b * per_img;
+  const int nb = r % NBI; r /= NBI;
+  int side, seg;                                           // 0 top, 1 bottom, 2 left, 3 right
+  if (r < 2 * seg_tb) { side = r / seg_tb; seg = r - side * seg_tb; }
+  else { r -= 2 * seg_tb; side = 2 + r / seg_lr; seg = r % seg_lr; }
+  const int px = lane & 15, kq = lane >> 4;
+  int qy, qx;
+  bool valid;
+  if (side < 2) { qy = side == 0 ? 0 : H - 1; qx = seg * 16 + px; valid = qx < W; }
+  else { qx = side == 2 ? 0 : W - 1; qy = 1 + seg * 16 + px; valid = qy <= H - 2; }
+  if (!valid) { qy = 0; qx = 0; }                          // masked lanes: every load below takes the out-of-range offset
+  const float* wbase = wd + (size_t)nb * NQ * 9 * 256 + lane * 4;       // wd[nb][q][tap'][lane][4]
+  const __amdgpu_buffer_rsrc_t rdy = make_rsrc(dy, (unsigned)B * (unsigned)H * (unsigned)W * (unsigned)Cout * 2u);
+  auto src = [&](int y, int x, bool ok, int q) {           // 4 channels of dy at (y, x), zeros when !ok
+    const unsigned voff = ok ? (unsigned)((b * H + y) * W + x) * (unsigned)Cout * 4u + (unsigned)kq * 16u : OOB;
+    return aload4<true>(rdy, voff, (unsigned)q * 64u);
+  };
+  f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int q = 0; q < NQ; ++q) {
+#pragma unroll
+    for (int tp = 0; tp < 9; ++tp) {
+      const int ty = tp / 3 - 1, tx = tp % 3 - 1;          // forward tap; pack index flipped: 8 - tp
+      const int y0 = qy - ty, x0 = qx - tx;
+      const bool y0ok = y0 >= 0 && y0 < H, x0ok = x0 >= 0 && x0 < W;
+      const bool y1ok = (qy == 0 && ty == -1) || (qy == H - 1 && ty == 1);
+      const bool x1ok = (qx == 0 && tx == -1) || (qx == W - 1 && tx == 1);
+      const float4 s00 = src(y0, x0, valid && y0ok && x0ok, q), s10 = src(qy, x0, valid && y1ok && x0ok, q);
+      const float4 s01 = src(y0, qx, valid && y0ok && x1ok, q), s11 = src(qy, qx, valid && y1ok && x1ok, q);
+      const float4 bv = make_float4((s00.x + s10.x) + (s01.x + s11.x), (s00.y + s10.y) + (s01.y + s11.y),
+                                    (s00.z + s10.z) + (s01.z + s11.z), (s00.w + s10.w) + (s01.w + s11.w));
+      const float4 w = round_bf16x4(ld4(wbase + ((size_t)q * 9 + (8 - tp)) * 256));   // same products as the bf16 MFMA of the main kernel
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, bv.x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, bv.y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, bv.z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, bv.w, acc, 0, 0, 0);
+    }
+  }
+  if (valid) {
+    // D rows = ci 4*kq + r, col = pixel
+    const size_t pix_o = (size_t)(b * H + qy) * W + qx;
+    const int ci_o = 16 * nb + 4 * kq;
+    float4 v = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    if (addend != nullptr) {
+      const float4 ad = ldA4<true>(addend, pix_o * Cin + ci_o);
+      v.x += ad.x; v.y += ad.y; v.z += ad.z; v.w += ad.w;
+    }
+    if (ci_o < split_ch) stA4<true>(g0, pix_o * C0 + ci_o, v);
+    else stA4<true>(g1, pix_o * C1 + (ci_o - split_ch), v);
+  }
+}
+
 }  // namespace
 
 // Number of persistent workgroups (== rows of stat_partials written) for a B x H x W conv with cout outputs:
@@ -1176,6 +1247,16 @@ int launch_dgrad_border_fix(const float* dy, int Cout, const float* wdg_layer, i
   const int waves = B * (2 * ((W + 15) / 16) + 2 * ((H - 2 + 15) / 16)) * (Cin / 16);
   hipLaunchKernelGGL(dgrad_border_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, dy, Cout, wdg_layer, Cin, g0, C0,
                      split_ch, g1, C1, B, H, W, bf16, bn_y, bn_scale, bn_shift, bn_partials, masked);
+  SIFSR_LAUNCH_CHECK();
+  return SIFSR_OK;
+}
+
+int launch_dgrad_border_whole_bf16(const float* dy, int Cout, const float* wdg_layer, int Cin, float* g0, int C0, int split_ch,
+                                   float* g1, int C1, const float* addend, int B, int H, int W, hipStream_t s) {
+  if (H < 3 || W < 2 || Cin % 16 || Cout % 16) return SIFSR_ERR_SHAPE;
+  const int waves = dgrad_border_waves(B, H, W, Cin);
+  hipLaunchKernelGGL(dgrad_border_whole_bf16_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, dy, Cout, wdg_layer, Cin, g0, C0,
+                     split_ch, g1, C1, addend, B, H, W);
   SIFSR_LAUNCH_CHECK();
   return SIFSR_OK;
 }

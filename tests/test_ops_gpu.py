@@ -404,8 +404,14 @@ def test_adam_flat(L):
 @pytest.mark.parametrize("shape", [(16, 16, 256, 256, 2), (16, 16, 128, 128, 8), (32, 16, 256, 256, 1),
                                    (64, 32, 128, 128, 4), (64, 64, 32, 32, 16), (128, 64, 64, 64, 4), (32, 64, 64, 64, 16)])
 def test_conv3x3_full_size_grids(L, shape):
-    """Layer-sized problems: enough tiles that the persistent kernels run two workgroups per CU and several
-    tiles per workgroup (the small cases above never do) -- forward and dgrad, repeated to expose races."""
+    """Layer-sized problems: enough tiles that the persistent kernels fill every CU (two workgroups per CU where the variant
+    reaches that residency; the small cases above never do) -- forward and dgrad, repeated to expose races.
+    Several tiles per workgroup happen in two calls only: sifsr_conv3x3_dgrad_wino at (16, 16, 256, 256, 2) and at
+    (16, 16, 128, 128, 8) -- 512 tiles on the 256 workgroups of the one-per-CU Winograd input gradient, two tiles each, with a
+    power-of-two tile grid, the XCD mapping, an even split and no partial tiles.  Every other call here stays at
+    ntiles <= conv3x3_grid_blocks(), one tile per workgroup (512 tiles on 512 workgroups for the 16-channel forward and
+    tap-domain calls, 256 or fewer tiles elsewhere).  The multi-tile walk in its other forms (plain stride, generic tile
+    index, uneven split, three rounds, partial tiles) is tests/test_tile_walk_gpu.py."""
     cin, cout, H, W, B = shape
     rs = np.random.RandomState(sum(shape))
     x = rnd(rs, B, cin, H, W)
