@@ -12,6 +12,9 @@ Drop-in surface (SURVEY.md §8 b):
   metrics.psnr_skimage / ssim_skimage  <- utils.py:548-578 (on device)
   metrics.aster_metrics / gradient_strata  <- model_perf_aster_formatds.py:371-437 (per-pair table; us.gssim, utils.py:1904-2005)
   fourier.fft2_magnitude / attenuation_spectra / get_FRR / get_FRO / get_FRU  <- compare_methods.py:312-324, utils.py:598-662
+  spectra.fft2_magnitude / attenuation_spectra / spectral_scores / summary_rows  <- compare_methods.py:305-417: the same for rasters
+                                       of any size and lists of mixed sizes (chirp-z FFT, include/sifsr_spectra.h), the table's four
+                                       spectral columns and the seven summary rows
   baselines.tsharp / atprk / aatprk    <- utils.py:1213-1253, :1588-1606 (the paper's comparison methods, on device)
   gaps.fill_gaps / select_tiles / predict_granule_gaps (also in predict)  <- no counterpart: cloud / ocean / fill pixels of a granule
                                        filled, all-gap tiles skipped, the output masked (include/sifsr_gaps.h)
@@ -35,7 +38,7 @@ and registers ``sifsr`` / ``sifsr.<submodule>`` as aliases of the same module ob
 import importlib
 import sys
 
-_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "gaps", "conserve", "predict", "baselines", "products", "lpips")
+_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "predict", "baselines", "products", "lpips")
 for _m in _SUBMODULES:
     importlib.import_module(__name__ + "." + _m)
 

@@ -4,6 +4,9 @@
 // Hand-written 2-D FFT (radix-2, in LDS, float64 -- an evaluation-time operator on a handful of 256x256
 // images; accuracy matters more than rate here: the attenuation spectra go down to -60 dB) + magnitude written
 // at the fftshift-ed position, then the ring means of the magnitude around the DC bin.
+// Sides that are not powers of two go through Bluestein's chirp-z transform over the same butterfly (include/sifsr_spectra.h).
+#include "../../include/sifsr_spectra.h"
+
 #include "edge_conv.h"
 
 namespace {
@@ -66,7 +69,7 @@ __global__ void fft_cols_mag_kernel(const cplx* __restrict__ spec, float* __rest
   }
   __syncthreads();
   fft_lds(x, tw, lgH, tid);
-  const int us = (u + W / 2) & (W - 1);
+  const int us = (u + W / 2) % W;   // W need not be a power of two when the row pass was the chirp one
   for (int v = tid; v < H; v += blockDim.x) {
     const int vs = (v + H / 2) & (H - 1);
     const double m = sqrt(x[v].re * x[v].re + x[v].im * x[v].im);
@@ -130,8 +133,125 @@ __global__ void ring_final_kernel(const double* __restrict__ part, const double*
   }
 }
 
+// ---- any length: Bluestein's chirp-z over the butterfly above (include/sifsr_spectra.h) ----------------------
+// One axis of length N, M = 1 << lgM the smallest power of two >= 2N - 1:
+//   w[n] = exp(-i pi n^2 / N),  a[n] = x[n] w[n] (zero up to M),  b[n] = conj(w[|n|]) circular,
+//   X[k] = w[k] IFFT_M(FFT_M(a) FFT_M(b))[k].
+// n^2 is reduced mod 2N in integers before it becomes a phase (n <= 1023: n^2 fits an int): the argument of sincospi is then exact.
+__device__ __forceinline__ cplx chirp(int n, int N) {
+  double sn, cs;
+  sincospi(-(double)((n * n) % (2 * N)) / (double)N, &sn, &cs);
+  return {cs, sn};
+}
+
+__device__ __forceinline__ void twiddles_lds(cplx* tw, int M, int tid, int nthr) {
+  for (int k = tid; k < M / 2; k += nthr) {
+    double sn, cs;
+    sincospi(-2.0 * (double)k / (double)M, &sn, &cs);
+    tw[k] = {cs, sn};
+  }
+}
+
+// FFT_M(b), once per call and axis: one workgroup of M/2 threads -> filt[M] in the scratch buffer
+__global__ void chirp_filter_kernel(cplx* __restrict__ filt, int N, int lgM) {
+  extern __shared__ double smem[];
+  const int M = 1 << lgM;
+  cplx* x = reinterpret_cast<cplx*>(smem);
+  cplx* tw = x + M;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < M; i += blockDim.x) {
+    const int n = i < N ? i : (i > M - N ? M - i : -1);
+    cplx b = {0.0, 0.0};
+    if (n >= 0) { b = chirp(n, N); b.im = -b.im; }
+    x[bitrev(i, lgM)] = b;
+  }
+  twiddles_lds(tw, M, tid, blockDim.x);
+  __syncthreads();
+  fft_lds(x, tw, lgM, tid);
+  for (int i = tid; i < M; i += blockDim.x) filt[i] = x[i];
+}
+
+// x holds a[] at the bit-reversed slots (all M written), tw the twiddles; both visible (barrier passed).  On return
+// x[k] = conj(M * IFFT_M(FFT_M(a) filt)[k]): the inverse is conj(FFT(conj(.))) / M, and the caller undoes conj and M.
+__device__ __forceinline__ void chirp_convolve_lds(cplx* x, const cplx* tw, const cplx* __restrict__ filt, int lgM, int tid, int nthr) {
+  const int M = 1 << lgM;
+  fft_lds(x, tw, lgM, tid);
+  for (int i = tid; i < M; i += nthr) {
+    const cplx p = cmul(x[i], filt[i]);
+    x[i] = {p.re, -p.im};
+  }
+  __syncthreads();
+  // back to bit-reversed order for the second transform: the pair (i, rev(i)) is swapped by the one thread that holds i < rev(i)
+  for (int i = tid; i < M; i += nthr) {
+    const int r = bitrev(i, lgM);
+    if (i < r) { const cplx t = x[i]; x[i] = x[r]; x[r] = t; }
+  }
+  __syncthreads();
+  fft_lds(x, tw, lgM, tid);
+}
+
+// row pass for a width that is not a power of two: one workgroup (M/2 threads) per (row, image)
+__global__ void chirp_rows_kernel(const float* __restrict__ img, cplx* __restrict__ spec, const cplx* __restrict__ filt,
+                                  int H, int W, int lgM) {
+  extern __shared__ double smem[];
+  const int M = 1 << lgM;
+  cplx* x = reinterpret_cast<cplx*>(smem);
+  cplx* tw = x + M;
+  const int tid = threadIdx.x;
+  const size_t row = (size_t)blockIdx.y * H + blockIdx.x;
+  const float* src = img + row * W;
+  for (int i = tid; i < M; i += blockDim.x) {
+    cplx a = {0.0, 0.0};
+    if (i < W) { const cplx w = chirp(i, W); const double v = (double)src[i]; a = {v * w.re, v * w.im}; }
+    x[bitrev(i, lgM)] = a;
+  }
+  twiddles_lds(tw, M, tid, blockDim.x);
+  __syncthreads();
+  chirp_convolve_lds(x, tw, filt, lgM, tid, blockDim.x);
+  cplx* dst = spec + row * W;
+  const double inv = 1.0 / (double)M;
+  for (int k = tid; k < W; k += blockDim.x) {
+    const cplx y = {x[k].re * inv, -x[k].im * inv};
+    dst[k] = cmul(chirp(k, W), y);
+  }
+}
+
+// column pass for a height that is not a power of two: one workgroup (M/2 threads) per (column, image); magnitude at the
+// fftshift-ed position (k + N/2) % N on both axes
+__global__ void chirp_cols_mag_kernel(const cplx* __restrict__ spec, const cplx* __restrict__ filt, float* __restrict__ mag,
+                                      double* __restrict__ mag64, int H, int W, int lgM) {
+  extern __shared__ double smem[];
+  const int M = 1 << lgM;
+  cplx* x = reinterpret_cast<cplx*>(smem);
+  cplx* tw = x + M;
+  const int tid = threadIdx.x;
+  const int u = blockIdx.x;
+  const size_t ib = (size_t)blockIdx.y * H * W;
+  for (int i = tid; i < M; i += blockDim.x) {
+    cplx a = {0.0, 0.0};
+    if (i < H) a = cmul(spec[ib + (size_t)i * W + u], chirp(i, H));
+    x[bitrev(i, lgM)] = a;
+  }
+  twiddles_lds(tw, M, tid, blockDim.x);
+  __syncthreads();
+  chirp_convolve_lds(x, tw, filt, lgM, tid, blockDim.x);
+  const int us = (u + W / 2) % W;
+  const double inv = 1.0 / (double)M;
+  for (int v = tid; v < H; v += blockDim.x) {
+    const int vs = (v + H / 2) % H;
+    const double m = sqrt(x[v].re * x[v].re + x[v].im * x[v].im) * inv;   // |w[v]| = 1: the last chirp factor does not reach |X|
+    if (mag) mag[ib + (size_t)vs * W + us] = (float)m;
+    if (mag64) mag64[ib + (size_t)vs * W + us] = m;
+  }
+}
+
 int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+bool radix2_side(int v) { return pow2(v) && v >= 4 && v <= 2048; }
+bool chirp_side(int v) { return !pow2(v) && v >= 4 && v <= 1024; }
+// length of the chirp transform's power-of-two convolution; 0 for a side the radix-2 pass takes
+int chirp_m(int v) { return chirp_side(v) ? 1 << ilog2(2 * v - 1) : 0; }
+size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
 
@@ -154,6 +274,54 @@ int launch_fft2_attenuation(const float* img, int B, int H, int W, void* scratch
   if (spectrum != nullptr) {
     const int nr = (H / 2 < W / 2 ? H / 2 : W / 2) - 1;
     if (nr < 1) return SIFSR_ERR_SHAPE;
+    const int nblk = (H + 15) / 16;
+    hipLaunchKernelGGL(ring_partial_kernel, dim3(nblk, B), dim3(256), 0, s, mag64, H, W, nr, 16, part);
+    hipLaunchKernelGGL(ring_final_kernel, dim3(B), dim3(128), 0, s, part, mag64, nblk, nr, H, W, spectrum);
+  }
+  SIFSR_LAUNCH_CHECK();
+  return SIFSR_OK;
+}
+
+// ---- include/sifsr_spectra.h: the same two outputs for sides that need not be powers of two -----------------------------------------
+// scratch = [the layout of fourier_scratch_bytes | FFT_M(b) of the row axis | FFT_M(b) of the column axis], the last two only for
+// an axis the chirp pass takes.
+size_t sifsrf_fft2_attenuation_scratch_bytes(int B, int H, int W) {
+  if (B < 1 || !(radix2_side(H) || chirp_side(H)) || !(radix2_side(W) || chirp_side(W))) return 0;
+  return align16(fourier_scratch_bytes(B, H, W)) + ((size_t)chirp_m(W) + (size_t)chirp_m(H)) * sizeof(cplx);
+}
+
+int sifsrf_fft2_attenuation(const float* img, int B, int H, int W, void* scratch, size_t scratch_bytes, float* mag, float* spectrum,
+                            void* stream) {
+  if (!img || !scratch || (!mag && !spectrum)) return SIFSR_ERR_ARG;
+  const size_t need = sifsrf_fft2_attenuation_scratch_bytes(B, H, W);
+  if (need == 0) return SIFSR_ERR_SHAPE;
+  if (scratch_bytes < need) return SIFSR_ERR_WORKSPACE;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int mw = chirp_m(W), mh = chirp_m(H);
+  if (mw == 0 && mh == 0) return launch_fft2_attenuation(img, B, H, W, scratch, mag, spectrum, s);   // today's path, today's bits
+  const size_t npx = (size_t)B * H * W;
+  cplx* spec = reinterpret_cast<cplx*>(scratch);
+  double* mag64 = reinterpret_cast<double*>(reinterpret_cast<char*>(scratch) + npx * 16);
+  double* part = mag64 + npx;
+  cplx* filt_w = reinterpret_cast<cplx*>(reinterpret_cast<char*>(scratch) + align16(fourier_scratch_bytes(B, H, W)));
+  cplx* filt_h = filt_w + mw;
+  const int nr = (H / 2 < W / 2 ? H / 2 : W / 2) - 1;
+  if (spectrum != nullptr && nr < 1) return SIFSR_ERR_SHAPE;
+  if (mw) {
+    const size_t lds = (size_t)(mw + mw / 2) * sizeof(cplx);
+    hipLaunchKernelGGL(chirp_filter_kernel, dim3(1), dim3(mw / 2), lds, s, filt_w, W, ilog2(mw));
+    hipLaunchKernelGGL(chirp_rows_kernel, dim3(H, B), dim3(mw / 2), lds, s, img, spec, filt_w, H, W, ilog2(mw));
+  } else {
+    hipLaunchKernelGGL(fft_rows_kernel, dim3(H, B), dim3(W / 2), (size_t)(W + W / 2) * 16, s, img, spec, H, W, ilog2(W));
+  }
+  if (mh) {
+    const size_t lds = (size_t)(mh + mh / 2) * sizeof(cplx);
+    hipLaunchKernelGGL(chirp_filter_kernel, dim3(1), dim3(mh / 2), lds, s, filt_h, H, ilog2(mh));
+    hipLaunchKernelGGL(chirp_cols_mag_kernel, dim3(W, B), dim3(mh / 2), lds, s, spec, filt_h, mag, mag64, H, W, ilog2(mh));
+  } else {
+    hipLaunchKernelGGL(fft_cols_mag_kernel, dim3(W, B), dim3(H / 2), (size_t)(H + H / 2) * 16, s, spec, mag, mag64, H, W, ilog2(H));
+  }
+  if (spectrum != nullptr) {
     const int nblk = (H + 15) / 16;
     hipLaunchKernelGGL(ring_partial_kernel, dim3(nblk, B), dim3(256), 0, s, mag64, H, W, nr, 16, part);
     hipLaunchKernelGGL(ring_final_kernel, dim3(B), dim3(128), 0, s, part, mag64, nblk, nr, H, W, spectrum);
