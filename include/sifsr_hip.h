@@ -118,7 +118,10 @@ SIFSR_API int sifsr_conv3x3_fwd_bf16(const float* src0, int C0, const float* sca
 SIFSR_API int sifsr_conv3x3_dgrad_bf16(const float* dy, int cout, const float* wdgrad, int cin, float* g0, int C0, float* g1,
                                        int C1, const float* addend, int B, int H, int W, void* stream);
 SIFSR_API size_t sifsr_conv3x3_wgrad_scratch_floats(int cin, int cout, int nblk);
-/* dw (OIHW) = sum_pixels dy (x) a_in; deterministic 2-stage reduction through `scratch`. */
+/* dw (OIHW) = sum_pixels dy (x) a_in; deterministic 2-stage reduction through `scratch`.  C0, C1 powers of two >= 16, cout
+ * 16, 32 or 64.  Cin = C0 + C1 is walked in 32-channel chunks, in 16-channel chunks when Cin / 16 is odd or the first of two
+ * sources has an odd number of 16-channel blocks; 64 output channels need 32-channel chunks (SIFSR_ERR_SHAPE otherwise, e.g.
+ * cat(16, 64) -> 64), as does the Winograd form below.  The same holds for the _fused, _bf16 and _wino entry points. */
 SIFSR_API int sifsr_conv3x3_wgrad(const float* src0, int C0, const float* scale0, const float* shift0,
                                   const float* src1, int C1, const float* scale1, const float* shift1,
                                   const float* dy, int cout, float* scratch, int nblk, float* dw, int B, int H, int W,

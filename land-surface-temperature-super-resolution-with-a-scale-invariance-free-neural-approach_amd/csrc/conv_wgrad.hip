@@ -407,9 +407,11 @@ size_t wgrad_slab_floats(int cin, int cout) { return (size_t)9 * cin * cout; }
 
 // Cin is processed in chunks of <= 32 channels (blockIdx.y): keeps LDS <= 76 KB so two workgroups fit a CU.
 // A chunk never straddles the two concatenated sources (16-channel chunks when the first has an odd
-// number of 16-channel blocks, e.g. ub3.convbloc.bloc.0 = cat(16, 16)).
+// number of 16-channel blocks, e.g. ub3.convbloc.bloc.0 = cat(16, 16)), and the chunks tile Cin exactly (16-channel
+// chunks when the total number of 16-channel blocks is odd, e.g. cat(32, 16): a 32-channel chunking would drop the last block
+// while the reduction still decodes it).
 int wgrad_nbi_chunk(const WgradArgs& a, int cin) {
-  if (cin < 32) return 1;
+  if (cin < 32 || (cin / 16) % 2) return 1;
   if (a.src[1].ptr != nullptr && (a.src[0].nq % 2)) return 1;
   return 2;
 }
@@ -426,6 +428,7 @@ int launch_conv3x3_wgrad(const WgradArgs& a, int cin, int cout, int nblk, hipStr
     if (!pow2(a.src[0].C) || (a.src[1].ptr && !pow2(a.src[1].C))) return SIFSR_ERR_SHAPE;
   }
   const int nbi = wgrad_nbi_chunk(a, cin), chunks = (cin / 16) / nbi, nbo = cout / 16;
+  if ((cin / 16) % nbi) return SIFSR_ERR_SHAPE;      // the chunks must tile Cin: the reduction decodes every block
   const bool dyf = a.dy_y != nullptr;
   if (dyf && !a.dy_coef) return SIFSR_ERR_ARG;
 #define SIFSR_WG(NBOV, NBIV)                                                                                                   \

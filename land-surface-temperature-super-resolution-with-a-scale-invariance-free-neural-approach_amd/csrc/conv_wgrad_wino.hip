@@ -315,8 +315,9 @@ int launch_xw(const WgradArgs& a, int chunks, int halves, int nblk, hipStream_t 
 
 }  // namespace
 
-// 16-channel blocks per cin chunk (blockIdx.y): 32-channel chunks from 32 input channels on, also across the two sources
-int wgrad_wino_nbi_chunk(int cin) { return cin < 32 ? 1 : 2; }
+// 16-channel blocks per cin chunk (blockIdx.y): 32-channel chunks from 32 input channels on, also across the two sources;
+// 16-channel chunks when the number of 16-channel blocks is odd (cat(16, 32)), so that the chunks tile Cin exactly
+int wgrad_wino_nbi_chunk(int cin) { return (cin < 32 || (cin / 16) % 2) ? 1 : 2; }
 
 bool conv3x3_wgrad_use_wino(const WgradArgs& a, int cin, int cout) {
   const int nbo = cout / 16, nbi = wgrad_wino_nbi_chunk(cin);
@@ -339,6 +340,7 @@ int launch_conv3x3_wgrad_wino(const WgradArgs& a, int cin, int cout, int nblk, h
   const bool dyf = a.dy_y != nullptr;
   if (dyf && !a.dy_coef) return SIFSR_ERR_ARG;
   const int nbi = wgrad_wino_nbi_chunk(cin), chunks = (cin / 16) / nbi, nbo = cout / 16;
+  if ((cin / 16) % nbi) return SIFSR_ERR_SHAPE;      // the chunks must tile Cin: the reduction decodes every block
 #define SIFSR_XW(NBOV, NBIV, HV)                                                                                     \
   if (nbo == NBOV * HV && nbi == NBIV)                                                                              \
     return dyf ? launch_xw<NBOV, NBIV, true>(a, chunks, HV, nblk, s) : launch_xw<NBOV, NBIV, false>(a, chunks, HV, nblk, s);
