@@ -12,6 +12,8 @@ training scripts use, the hot-path ones on MI355X:
                                                                              (A = -0.75, half-pixel centres, edge clamp)
   us.TsHARP, us.ATPRK, us.AATPRK                   utils.py:1213-1253, :1588-1606 -> device kernels + host variogram fit
                                                                              (sifsr.baselines); 2-D numpy in, float64 numpy out
+  us.downscale_Aster_to_coarse, us.downscale_Aster_to_fine, us.generic_downscale   utils.py:1759-1830, :1642-1668 -> device kernels
+                                                                             (sifsr.degrade): the sensor model at any ratio
   us.DMS                                           data_mining_sharpener_modified.py as model_perf_aster_formatds.py:220-250
                                                                              calls it -> device kernels (sifsr.baselines.dms)
 
@@ -136,6 +138,38 @@ def DMS(temp_coarse, index_fine, scale, n_estimators=10, seed=0):
             raise ValueError(f"DMS: {what} must be a 2-D array, got shape {a.shape}")
         args.append(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)[None, None])
     return baselines.dms(*args, n_estimators=n_estimators, seed=seed)[0, 0].cpu().numpy().astype(np.float64)
+
+
+def _same(name, padding):
+    if padding != "same":
+        raise NotImplementedError(f"{name}: only padding='same' (what the reference runs with) has a gfx950 kernel, got {padding!r}")
+
+
+def _aster(name, data, factor, mtf, padding, hkw):
+    from sifsr import degrade
+    _same(name, padding)
+    a = np.asarray(data)
+    if a.ndim != 2:
+        raise ValueError(f"{name}: data must be a 2-D array, got shape {a.shape}")
+    t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(torch.device("cuda", torch.cuda.current_device()))
+    return degrade.degrade(t, factor, mtf=mtf, hkw=hkw).cpu().numpy()
+
+
+def downscale_Aster_to_coarse(data, factor=926.25 / 90, mtf=0.1, padding="same", hkw=None):
+    """utils.py:1759-1793: 2-D numpy (90 m) -> 2-D float32 numpy (926.25 m)."""
+    return _aster("downscale_Aster_to_coarse", data, factor, mtf, padding, hkw)
+
+
+def downscale_Aster_to_fine(data, factor=231.656 / 90, mtf=0.1, padding="same", hkw=None):
+    """utils.py:1796-1830: 2-D numpy (90 m) -> 2-D float32 numpy (231.656 m)."""
+    return _aster("downscale_Aster_to_fine", data, factor, mtf, padding, hkw)
+
+
+def generic_downscale(data, factor=2.0, mtf=0.1, padding="same", hkw=3):
+    """utils.py:1642-1668: (B,C,H,W) device tensor -> device tensor."""
+    from sifsr import degrade
+    _same("generic_downscale", padding)
+    return degrade.degrade(data, factor, mtf=mtf, hkw=hkw)
 
 
 def _read(file, keys):

@@ -28,6 +28,9 @@ Drop-in surface (SURVEY.md §8 b):
   conserve.consistency / conserve, predict_granule(conserve=) / predict_granule_gaps(conserve=) / GranulePredictor(conserve=)  <- no
                                        counterpart for the network (TsHARP's correction_linreg, utils.py:897, is the baselines' form):
                                        the residual LST - D(SR) over the valid cells and its correction (include/sifsr_conserve.h)
+  degrade.degrade / aster_to_coarse / aster_to_fine / generic_downscale / simulate_pair / output_shape  <- utils.py:1642-1668,
+                                       :1759-1830: the sensor model at any ratio (ASTER 90 m -> 250 m / 1 km), with the validity of
+                                       every output (include/sifsr_degrade.h)
   products.decode / PatchMiner / MinedPatches, dataset.MinedDataset  <- process_modis.py:38-335, data_preparation.py:32-102
                                        (raw granule arrays -> patches + statistics.json, on device)
 
@@ -38,7 +41,7 @@ and registers ``sifsr`` / ``sifsr.<submodule>`` as aliases of the same module ob
 import importlib
 import sys
 
-_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "predict", "baselines", "products", "lpips")
+_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "degrade", "predict", "baselines", "products", "lpips")
 for _m in _SUBMODULES:
     importlib.import_module(__name__ + "." + _m)
 
@@ -52,3 +55,5 @@ from .sif_ops import masked_sif_loss, masked_sif_loss_with_grad  # noqa: E402,F4
 from .optim import FlatAdam  # noqa: E402,F401
 from .dataset import ModisDatasetB, MinedDataset  # noqa: E402,F401
 from ._lib import SifsrError  # noqa: E402,F401
+# (`sifsr.degrade` stays the module: its function of the same name is `sifsr.degrade.degrade`)
+from .degrade import aster_to_coarse, aster_to_fine, generic_downscale, simulate_pair  # noqa: E402,F401

@@ -1,0 +1,256 @@
+// The sensor model at any ratio (C ABI and every definition: include/sifsr_degrade.h): reflect pad, Gaussian PSF
+// with the reference's zero ring, bicubic resampling by a non-integer factor, as one banded operator per axis, out = Ry . x . Rx^T.
+//
+//  * degrade_table_kernel   one thread per weight of an axis (blockIdx.y: 0 rows, 1 columns).  From the fp32 source coordinate of
+//    F.interpolate it forms, in float64, one of the K = 2 hw + 4 weights of its output over consecutive ORIGINAL pixels -- reflection
+//    and zero ring folded in --; the thread of tap 0 also stores the first pixel of that window, the stencil [lo, hi] (the pixels a
+//    non-zero coefficient reaches) and the "touches the ring" flag.  Row weights are stored [output][tap] (a wave of the row pass reads one output's taps: scalar
+//    loads), column weights [tap][output] (the lanes of the column pass are consecutive outputs: coalesced).
+//  * degrade_rows_kernel    the large pass, and the coalesced one: a wave owns 64 consecutive columns of ONE output row and walks the
+//    K input rows of its window; weights and row indices are wave-uniform.  Only the rows some output samples are read: at factor
+//    10.3 the reference blurs a hundred pixels for each one it keeps.  Writes the (B, oh, w) float64 intermediate and, with `valid`,
+//    one byte per entry: the column of the stencil is all valid.
+//  * degrade_cols_kernel    a lane owns one output; it walks K consecutive entries of the intermediate row, 1 / factor of the
+//    first pass' data.  Validity, fill value and the single rounding to fp32 happen here.
+// No LDS, no atomics, no allocation, no host synchronisation; nothing depends on the order in which workgroups run.
+#include "../../include/sifsr_degrade.h"
+
+#include <math.h>
+
+#include "common.h"
+
+namespace {
+
+constexpr int BX = 64;         // outputs (columns) per wave
+constexpr int BY = 4;          // output rows per workgroup: one per wave
+constexpr int MAX_HW = 16;
+constexpr int MAX_SIDE = 16384;
+constexpr int MAX_BATCH = 65535;
+
+struct Axis {
+  int n, n_pad, count, cut;    // original length, padded length, outputs after the crop, outputs cut on each side
+};
+
+struct Psf {
+  double g[2 * MAX_HW + 1];
+  int hw;
+  float scale;                 // (float)(1.0 / (1.0 / factor))
+};
+
+struct Plan {
+  int hw, K, oh, ow;
+  Axis ay, ax;
+  size_t wy_off, wx_off, my_off, mx_off, tmp_off, tv_off, bytes;
+};
+
+// the original pixels that the blurred entries q_lo .. q_hi read, after the reflection: [*lo, *hi]
+__device__ __forceinline__ void fold_range(int q_lo, int q_hi, int hw, int n, int n_pad, int* lo, int* hi) {
+  const int i_lo = max(q_lo - hw, 0) - hw;                // >= -hw, <= n - 1
+  const int i_hi = min(q_hi + hw, n_pad - 1) - hw;        // >= 0,   <= n - 1 + hw
+  int a = max(i_lo, 0), b = min(i_hi, n - 1);            // read directly: never empty
+  if (i_lo < 0) { a = 0; b = max(b, -i_lo); }             // mirrored at the low edge: 1 .. -i_lo (hw <= n - 1)
+  if (i_hi >= n) a = min(a, 2 * (n - 1) - i_hi);          // mirrored at the high edge: 2 (n - 1) - i_hi .. n - 2, and b = n - 1
+  *lo = a;
+  *hi = b;
+}
+
+__global__ __launch_bounds__(256) void degrade_table_kernel(const Psf p, const Axis ay, const Axis ax, double* __restrict__ wy,
+                                                            double* __restrict__ wx, int4* __restrict__ my, int4* __restrict__ mx) {
+#pragma clang fp contract(off)
+  const bool rows = blockIdx.y == 0;
+  const Axis A = rows ? ay : ax;
+  const int hw = p.hw, K = 2 * hw + 4, n = A.n;
+  const int e = blockIdx.x * 256 + threadIdx.x;           // the index of the weight in its table, either layout
+  if (e >= A.count * K) return;
+  const int o = rows ? e / K : e % A.count, k = rows ? e % K : e / A.count;
+  // the source coordinate as upsample_bicubic2d forms it, every step rounded to fp32
+  const float s = __fsub_rn(__fmul_rn(p.scale, __fadd_rn((float)(o + A.cut), 0.5f)), 0.5f);
+  const float fl = floorf(s);
+  const double t = (double)__fsub_rn(s, fl);
+  const int f = (int)fl;
+  const double a = -0.75, u = 1.0 - t;
+  double c[4];
+  c[0] = ((a * (t + 1.0) - 5.0 * a) * (t + 1.0) + 8.0 * a) * (t + 1.0) - 4.0 * a;
+  c[1] = ((a + 2.0) * t - (a + 3.0)) * t * t + 1.0;
+  c[2] = ((a + 2.0) * u - (a + 3.0)) * u * u + 1.0;
+  c[3] = ((a * (u + 1.0) - 5.0 * a) * (u + 1.0) + 8.0 * a) * (u + 1.0) - 4.0 * a;
+  int q[4], q_lo = A.n_pad, q_hi = -1, ring = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    q[i] = clampi(f - 1 + i, 0, A.n_pad - 1);
+    if (c[i] != 0.0) {
+      q_lo = min(q_lo, q[i]);
+      q_hi = max(q_hi, q[i]);
+      ring |= (q[i] < hw || q[i] > A.n_pad - 1 - hw) ? 1 : 0;
+    }
+  }
+  int start, last, lo, hi;
+  fold_range(q[0], q[3], hw, n, A.n_pad, &start, &last);  // last - start < K: the window holds every weight
+  fold_range(q_lo, q_hi, hw, n, A.n_pad, &lo, &hi);       // c[1] and c[2] are never both 0: q_lo <= q_hi
+  (void)last;
+  const int j = start + k;
+  double w = 0.0;
+  if (j < n) {
+    // the padded entries that hold pixel j: itself, its mirror at the low edge, its mirror at the high edge
+    const int cand[3] = {j + hw, hw - j, 2 * (n - 1) - j + hw};
+    const bool use[3] = {true, j >= 1 && j <= hw, j <= n - 2 && n - 1 - j <= hw};
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      if (!use[m]) continue;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int d = cand[m] - q[i];
+        if (d >= -hw && d <= hw) w += c[i] * p.g[d + hw];
+      }
+    }
+  }
+  (rows ? wy : wx)[e] = w;
+  if (k == 0) (rows ? my : mx)[o] = make_int4(start, lo, hi, ring);
+}
+
+// grid (ceil(w / BX), ceil(oh / BY), B), 256 threads: wave v of the workgroup owns output row blockIdx.y * BY + v
+__global__ __launch_bounds__(256) void degrade_rows_kernel(const float* __restrict__ x, const unsigned char* __restrict__ valid,
+                                                           const double* __restrict__ wy, const int4* __restrict__ my,
+                                                           double* __restrict__ tmp, unsigned char* __restrict__ tv, int h, int w,
+                                                           int oh, int K) {
+  const int oy = __builtin_amdgcn_readfirstlane(blockIdx.y * BY + (threadIdx.x >> 6));
+  const int col = blockIdx.x * BX + (threadIdx.x & 63);
+  if (oy >= oh || col >= w) return;
+  const int4 m = my[oy];
+  const double* wk = wy + (size_t)oy * K;
+  const size_t img = (size_t)blockIdx.z * h * w;
+  const float* src = x + img + col;
+  double acc = 0.0;
+  // no branch in the loop, so that the loads of several taps are in flight together; a window that ends past the raster has zero
+  // weights there and reads the last row instead, and what lies under a zero weight (a NaN of an invalid pixel) is not used
+#pragma unroll 8
+  for (int k = 0; k < K; ++k) {
+    const double wgt = wk[k];
+    const double v = (double)src[(size_t)min(m.x + k, h - 1) * w];
+    acc = wgt != 0.0 ? fma(wgt, v, acc) : acc;
+  }
+  const size_t dst = ((size_t)blockIdx.z * oh + oy) * w + col;
+  tmp[dst] = acc;
+  if (valid != nullptr) {
+    const unsigned char* v = valid + img + col;
+    int ok = 1;
+#pragma unroll 4
+    for (int j = m.y; j <= m.z; ++j) ok &= v[(size_t)j * w] != 0 ? 1 : 0;
+    tv[dst] = (unsigned char)ok;
+  }
+}
+
+// grid (ceil(ow / BX), ceil(oh / BY), B), 256 threads: lane = output column, wave = output row
+__global__ __launch_bounds__(256) void degrade_cols_kernel(const double* __restrict__ tmp, const unsigned char* __restrict__ tv,
+                                                           const double* __restrict__ wx, const int4* __restrict__ my,
+                                                           const int4* __restrict__ mx, float* __restrict__ out,
+                                                           unsigned char* __restrict__ out_valid, int w, int oh, int ow, int K,
+                                                           int with_valid, float fill_value) {
+  const int oy = __builtin_amdgcn_readfirstlane(blockIdx.y * BY + (threadIdx.x >> 6));
+  const int ox = blockIdx.x * BX + (threadIdx.x & 63);
+  if (oy >= oh || ox >= ow) return;
+  const int4 m = mx[ox];
+  const size_t row = ((size_t)blockIdx.z * oh + oy) * w;
+  const double* src = tmp + row;
+  double acc = 0.0;
+#pragma unroll 4
+  for (int k = 0; k < K; ++k) {
+    const double wgt = wx[(size_t)k * ow + ox];
+    const double v = src[min(m.x + k, w - 1)];
+    acc = wgt != 0.0 ? fma(wgt, v, acc) : acc;             // what lies under a zero weight (a NaN of an invalid pixel) is not used
+  }
+  int ok = (my[oy].w | m.w) == 0 ? 1 : 0;
+  if (with_valid) {
+    const unsigned char* v = tv + row;
+    for (int j = m.y; j <= m.z; ++j) ok &= v[j];
+  }
+  const size_t dst = ((size_t)blockIdx.z * oh + oy) * ow + ox;
+  out[dst] = (with_valid && !ok) ? fill_value : (float)acc;
+  if (out_valid != nullptr) out_valid[dst] = (unsigned char)ok;
+}
+
+bool axis_of(int n, double factor, int hw, int crop, Axis* a) {
+  if (n < hw + 1 || n > MAX_SIDE) return false;
+  a->n = n;
+  a->n_pad = n + 2 * hw;
+  a->cut = crop ? (int)((double)hw / factor) : 0;
+  a->count = (int)floor((double)a->n_pad * (1.0 / factor)) - 2 * a->cut;
+  return a->count >= 1;
+}
+
+size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+bool plan_of(int B, int h, int w, double factor, int hkw, int crop, Plan* p) {
+  if (!(factor > 1.0 && factor <= 16.0) || hkw < 0 || B < 1 || B > MAX_BATCH || (crop != 0 && crop != 1)) return false;
+  p->hw = hkw == 0 ? (int)ceil(factor) : hkw;
+  if (p->hw < 1 || p->hw > MAX_HW) return false;
+  if (!axis_of(h, factor, p->hw, crop, &p->ay) || !axis_of(w, factor, p->hw, crop, &p->ax)) return false;
+  p->K = 2 * p->hw + 4;
+  p->oh = p->ay.count;
+  p->ow = p->ax.count;
+  const size_t mid = (size_t)B * p->oh * w;
+  p->wy_off = 0;
+  p->wx_off = up16((size_t)p->oh * p->K * sizeof(double));
+  p->my_off = p->wx_off + up16((size_t)p->ow * p->K * sizeof(double));
+  p->mx_off = p->my_off + (size_t)p->oh * sizeof(int4);
+  p->tmp_off = p->mx_off + (size_t)p->ow * sizeof(int4);
+  p->tv_off = p->tmp_off + mid * sizeof(double);
+  p->bytes = up16(p->tv_off + mid);
+  return true;
+}
+
+bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+}  // namespace
+
+// ---- C ABI (include/sifsr_degrade.h) ----
+int sifsrs_out_shape(int h, int w, double factor, int hkw, int crop, int* oh, int* ow) {
+  if (!oh || !ow) return SIFSR_ERR_ARG;
+  Plan p;
+  if (!plan_of(1, h, w, factor, hkw, crop, &p)) return SIFSR_ERR_SHAPE;
+  *oh = p.oh;
+  *ow = p.ow;
+  return SIFSR_OK;
+}
+
+size_t sifsrs_workspace_bytes(int B, int h, int w, double factor, int hkw, int crop) {
+  Plan p;
+  return plan_of(B, h, w, factor, hkw, crop, &p) ? p.bytes : 0;
+}
+
+int sifsrs_degrade(const float* x, const unsigned char* valid, float* out, unsigned char* out_valid, void* workspace,
+                   size_t workspace_bytes, int B, int h, int w, double factor, double mtf, int hkw, int crop, float fill_value,
+                   void* stream) {
+  if (!x || !out || !workspace || !aligned(workspace, 16) || !aligned(x, 4) || !aligned(out, 4)) return SIFSR_ERR_ARG;
+  Plan p;
+  if (!plan_of(B, h, w, factor, hkw, crop, &p) || !(mtf > 0.0 && mtf < 1.0)) return SIFSR_ERR_SHAPE;
+  if (workspace_bytes < p.bytes) return SIFSR_ERR_WORKSPACE;
+
+  Psf psf;
+  const double pi = 3.14159265358979323846;
+  const double sigma = sqrt(-log(mtf) / 2.0) / (pi * (0.5 / factor));
+  double sum = 0.0;
+  for (int k = -p.hw; k <= p.hw; ++k) sum += (psf.g[k + p.hw] = exp(-((double)k * k) / (2.0 * sigma * sigma)));
+  for (int k = 0; k < 2 * MAX_HW + 1; ++k) psf.g[k] = k <= 2 * p.hw ? psf.g[k] / sum : 0.0;
+  psf.hw = p.hw;
+  psf.scale = (float)(1.0 / (1.0 / factor));
+
+  char* ws = static_cast<char*>(workspace);
+  double* wy = reinterpret_cast<double*>(ws + p.wy_off);
+  double* wx = reinterpret_cast<double*>(ws + p.wx_off);
+  int4* my = reinterpret_cast<int4*>(ws + p.my_off);
+  int4* mx = reinterpret_cast<int4*>(ws + p.mx_off);
+  double* tmp = reinterpret_cast<double*>(ws + p.tmp_off);
+  unsigned char* tv = reinterpret_cast<unsigned char*>(ws + p.tv_off);
+  hipStream_t s = (hipStream_t)stream;
+  const int most = (p.oh > p.ow ? p.oh : p.ow) * p.K;
+  hipLaunchKernelGGL(degrade_table_kernel, dim3((most + 255) / 256, 2), dim3(256), 0, s, psf, p.ay, p.ax, wy, wx, my, mx);
+  SIFSR_LAUNCH_CHECK();
+  const int gy = (p.oh + BY - 1) / BY;
+  hipLaunchKernelGGL(degrade_rows_kernel, dim3((w + BX - 1) / BX, gy, B), dim3(256), 0, s, x, valid, wy, my, tmp, tv, h, w, p.oh, p.K);
+  SIFSR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(degrade_cols_kernel, dim3((p.ow + BX - 1) / BX, gy, B), dim3(256), 0, s, tmp, tv, wx, my, mx, out, out_valid, w,
+                     p.oh, p.ow, p.K, valid != nullptr ? 1 : 0, fill_value);
+  SIFSR_LAUNCH_CHECK();
+  return SIFSR_OK;
+}
