@@ -31,6 +31,9 @@ Drop-in surface (SURVEY.md §8 b):
   degrade.degrade / aster_to_coarse / aster_to_fine / generic_downscale / simulate_pair / output_shape  <- utils.py:1642-1668,
                                        :1759-1830: the sensor model at any ratio (ASTER 90 m -> 250 m / 1 km), with the validity of
                                        every output (include/sifsr_degrade.h)
+  adapt.frozen_bn / input_gradient / tile_targets / adapt_granule, ModelB_2.bn_frozen  <- no counterpart: fine-tuning a trained
+                                       model on the granule it is about to predict -- BatchNorm backward with frozen running statistics,
+                                       the gradient with respect to the network input, loss targets of active tiles (include/sifsr_adapt.h)
   products.decode / PatchMiner / MinedPatches, dataset.MinedDataset  <- process_modis.py:38-335, data_preparation.py:32-102
                                        (raw granule arrays -> patches + statistics.json, on device)
 
@@ -41,7 +44,7 @@ and registers ``sifsr`` / ``sifsr.<submodule>`` as aliases of the same module ob
 import importlib
 import sys
 
-_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "degrade", "predict", "baselines", "products", "lpips")
+_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "degrade", "predict", "baselines", "products", "lpips", "adapt")
 for _m in _SUBMODULES:
     importlib.import_module(__name__ + "." + _m)
 

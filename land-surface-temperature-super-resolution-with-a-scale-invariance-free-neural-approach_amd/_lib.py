@@ -12,8 +12,9 @@ gated by ``tests/test_mosaic_host.py``), ``include/sifsr_baselines.h`` (prefix `
 ``tests/test_lpips_host.py``), ``include/sifsr_conserve.h`` (prefix ``sifsrk_``, gated by
 ``tests/test_conserve_host.py``), ``include/sifsr_dms.h`` (prefix ``sifsrd_``, gated by
 ``tests/test_dms_host.py``), ``include/sifsr_spectra.h`` (prefix ``sifsrf_``, gated by
-``tests/test_spectra_host.py``) and ``include/sifsr_degrade.h`` (prefix ``sifsrs_``, gated by
-``tests/test_degrade_host.py``).  There is NO fallback: if the library is missing or a call fails, we raise.
+``tests/test_spectra_host.py``), ``include/sifsr_degrade.h`` (prefix ``sifsrs_``, gated by
+``tests/test_degrade_host.py``) and ``include/sifsr_adapt.h`` (prefix ``sifsra_``, gated by
+``tests/test_adapt_host.py``).  There is NO fallback: if the library is missing or a call fails, we raise.
 """
 from __future__ import annotations
 
@@ -37,6 +38,7 @@ CONSERVE_HEADER = os.path.join(_ROOT, "include", "sifsr_conserve.h")
 DMS_HEADER = os.path.join(_ROOT, "include", "sifsr_dms.h")
 SPECTRA_HEADER = os.path.join(_ROOT, "include", "sifsr_spectra.h")
 DEGRADE_HEADER = os.path.join(_ROOT, "include", "sifsr_degrade.h")
+ADAPT_HEADER = os.path.join(_ROOT, "include", "sifsr_adapt.h")
 # SIFSR_LIB: another build of the same C ABI (same-device A/B of kernel variants, tools/ab/); default: the in-tree library
 LIB_PATH = os.environ.get("SIFSR_LIB") or os.path.join(_HERE, "libsifsr_hip.so")
 
@@ -86,7 +88,8 @@ def lib():
         _decls = {**parse_header(), **parse_header(EXTENSION_HEADER), **parse_header(BASELINES_HEADER),
                   **parse_header(PRODUCTS_HEADER), **parse_header(GAPS_HEADER), **parse_header(MASKED_HEADER),
                   **parse_header(SCORES_HEADER), **parse_header(LPIPS_HEADER), **parse_header(CONSERVE_HEADER),
-                  **parse_header(DMS_HEADER), **parse_header(SPECTRA_HEADER), **parse_header(DEGRADE_HEADER)}
+                  **parse_header(DMS_HEADER), **parse_header(SPECTRA_HEADER), **parse_header(DEGRADE_HEADER),
+                  **parse_header(ADAPT_HEADER)}
         for name, (ret, args) in _decls.items():
             fn = getattr(handle, name)     # AttributeError if the library lacks a declared symbol
             fn.restype = ret
@@ -152,6 +155,11 @@ def declared_spectra_symbols():
 def declared_degrade_symbols():
     """The names ``include/sifsr_degrade.h`` declares (``sifsrs_*``)."""
     return sorted(parse_header(DEGRADE_HEADER).keys())
+
+
+def declared_adapt_symbols():
+    """The names ``include/sifsr_adapt.h`` declares (``sifsra_*``)."""
+    return sorted(parse_header(ADAPT_HEADER).keys())
 
 
 def _conv(v):

@@ -141,16 +141,39 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* g, cons
 
 // fp32 coefficients of bn_bwd4 (common.h), [sc | sh | k1 | k0] with C floats each: dy = sc*dz + k1*z + k0 on the
 // forward's own pre-activation z = fma(y, sc, sh); k1 = -invstd*dgamma/N, k0 = -sc*dbeta/N - k1*beta (float64, rounded once).
+template <bool FROZEN = false>
 static __device__ __forceinline__ void write_coef_f(float* coef_f, int C, int c, const float* scale, const float* shift,
                                                     const float* invstd, const float* beta, double db, double dg, double count) {
   if (coef_f == nullptr) return;
-  const double k1 = -(double)invstd[c] * dg / count;
   coef_f[c] = scale[c];
   coef_f[C + c] = shift[c];
-  coef_f[2 * C + c] = (float)k1;
-  coef_f[3 * C + c] = (float)(-(double)scale[c] * db / count - k1 * (double)beta[c]);
+  if constexpr (FROZEN) {
+    coef_f[2 * C + c] = 0.f;
+    coef_f[3 * C + c] = 0.f;
+  } else {
+    const double k1 = -(double)invstd[c] * dg / count;
+    coef_f[2 * C + c] = (float)k1;
+    coef_f[3 * C + c] = (float)(-(double)scale[c] * db / count - k1 * (double)beta[c]);
+  }
+}
+// float64 [scale | k1 | k0] of dy = scale*dz + k1*y + k0
+template <bool FROZEN>
+static __device__ __forceinline__ void write_coef(double* coef, int C, int c, const float* scale, const float* mean, const float* invstd,
+                                                  double db, double dg, double count) {
+  coef[c] = (double)scale[c];
+  if constexpr (FROZEN) {
+    coef[C + c] = 0.0;
+    coef[2 * C + c] = 0.0;
+  } else {
+    const double k1 = -(double)scale[c] * (double)invstd[c] * dg / count;
+    coef[C + c] = k1;
+    coef[2 * C + c] = -(double)scale[c] * db / count - k1 * (double)mean[c];
+  }
 }
 
+// FROZEN (running-statistics BatchNorm, fine-tuning: DESIGN.md §9 f16): the statistics are constants of the backward, so dy = scale*dz --
+// k1 = k0 = 0 --, dbeta / dgamma keep their sums (the second sum carries the running mean / invstd the frozen forward left)
+template <bool FROZEN>
 __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __restrict__ partials, int nblk, int C,
                                                               double count, const float* __restrict__ scale,
                                                               const float* __restrict__ mean,
@@ -190,17 +213,14 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
     dgamma[c] = (float)dg;
     // dy = scale*dz + k1*y + k0, kept in float64: the three terms cancel to << |scale*dz| when the
     // incoming gradient is smooth (ATen's CPU kernel also evaluates this in acc_type<float> = double)
-    const double k1 = -(double)scale[c] * (double)invstd[c] * dg / count;
-    coef[c] = (double)scale[c];
-    coef[C + c] = k1;
-    coef[2 * C + c] = -(double)scale[c] * db / count - k1 * (double)mean[c];
-    write_coef_f(coef_f, C, c, scale, shift, invstd, beta, db, dg, count);
+    write_coef<FROZEN>(coef, C, c, scale, mean, invstd, db, dg, count);
+    write_coef_f<FROZEN>(coef_f, C, c, scale, shift, invstd, beta, db, dg, count);
   }
 }
 
 // Same, for sums produced by the dgrad epilogue + border kernel of the layer above (conv_mfma.hip): two partial arrays,
 // and the second sum is sum dz*y (not dz*xhat): sum dz*xhat = invstd * (sum dz*y - mean * sum dz), in float64.
-template <int NT>   // threads per channel: 1024 when there are thousands of partial rows (the upsample adjoint writes one per 8x8 pixels)
+template <int NT, bool FROZEN>   // threads per channel: 1024 when there are thousands of partial rows (the upsample adjoint writes one per 8x8 pixels)
 __global__ __launch_bounds__(NT) void bn_bwd_finalize2_kernel(const float* __restrict__ pa, int na,
                                                                const float* __restrict__ pb, int nb, int C, double count,
                                                                const float* __restrict__ scale,
@@ -220,11 +240,8 @@ __global__ __launch_bounds__(NT) void bn_bwd_finalize2_kernel(const float* __res
     const double dg = (double)invstd[c] * (s2 - (double)mean[c] * db);
     dbeta[c] = (float)db;
     dgamma[c] = (float)dg;
-    const double k1 = -(double)scale[c] * (double)invstd[c] * dg / count;
-    coef[c] = (double)scale[c];
-    coef[C + c] = k1;
-    coef[2 * C + c] = -(double)scale[c] * db / count - k1 * (double)mean[c];
-    write_coef_f(coef_f, C, c, scale, shift, invstd, beta, db, dg, count);
+    write_coef<FROZEN>(coef, C, c, scale, mean, invstd, db, dg, count);
+    write_coef_f<FROZEN>(coef_f, C, c, scale, shift, invstd, beta, db, dg, count);
   }
 }
 
@@ -310,27 +327,30 @@ int launch_bn_bwd_reduce(const float* g, const float* y, const float* scale, con
 
 int launch_bn_bwd_finalize(const float* partials, int nblk, int C, double count, const float* scale, const float* mean,
                            const float* invstd, float* dgamma, float* dbeta, double* coef, hipStream_t s, const float* shift,
-                           const float* beta, float* coef_f, const float* xs_partials, int xs_n, float* xs_out) {
+                           const float* beta, float* coef_f, const float* xs_partials, int xs_n, float* xs_out, int frozen) {
   if (coef_f != nullptr && (!shift || !beta)) return SIFSR_ERR_ARG;
   if (xs_partials != nullptr && (xs_n < 1 || !xs_out)) return SIFSR_ERR_ARG;
   const int extra = xs_partials != nullptr ? (xs_n + 3) / 4 : 0;
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C + extra), dim3(256), 0, s, partials, nblk, C, count, scale, mean, invstd,
-                     dgamma, dbeta, coef, shift, beta, coef_f, xs_partials, xs_n, xs_out);
+  if (frozen)
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel<true>, dim3(C + extra), dim3(256), 0, s, partials, nblk, C, count, scale, mean, invstd,
+                       dgamma, dbeta, coef, shift, beta, coef_f, xs_partials, xs_n, xs_out);
+  else
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel<false>, dim3(C + extra), dim3(256), 0, s, partials, nblk, C, count, scale, mean, invstd,
+                       dgamma, dbeta, coef, shift, beta, coef_f, xs_partials, xs_n, xs_out);
   SIFSR_LAUNCH_CHECK();
   return SIFSR_OK;
 }
 
 int launch_bn_bwd_finalize2(const float* pa, int na, const float* pb, int nb, int C, double count, const float* scale,
                             const float* mean, const float* invstd, float* dgamma, float* dbeta, double* coef, hipStream_t s,
-                            const float* shift, const float* beta, float* coef_f) {
+                            const float* shift, const float* beta, float* coef_f, int frozen) {
   if (coef_f != nullptr && (!shift || !beta)) return SIFSR_ERR_ARG;
   // NOTE: the result depends on the thread count (summation order), so the choice is a function of the row count alone
-  if (na + nb > 4096)
-    hipLaunchKernelGGL((bn_bwd_finalize2_kernel<1024>), dim3(C), dim3(1024), 0, s, pa, na, pb, nb, C, count, scale, mean, invstd, dgamma,
-                       dbeta, coef, shift, beta, coef_f);
-  else
-    hipLaunchKernelGGL((bn_bwd_finalize2_kernel<256>), dim3(C), dim3(256), 0, s, pa, na, pb, nb, C, count, scale, mean, invstd, dgamma,
-                       dbeta, coef, shift, beta, coef_f);
+#define BN_FIN2(NT_, FR_) hipLaunchKernelGGL((bn_bwd_finalize2_kernel<NT_, FR_>), dim3(C), dim3(NT_), 0, s, pa, na, pb, nb, C, count, scale, mean, \
+                                             invstd, dgamma, dbeta, coef, shift, beta, coef_f)
+  if (na + nb > 4096) { if (frozen) BN_FIN2(1024, true); else BN_FIN2(1024, false); }
+  else { if (frozen) BN_FIN2(256, true); else BN_FIN2(256, false); }
+#undef BN_FIN2
   SIFSR_LAUNCH_CHECK();
   return SIFSR_OK;
 }

@@ -48,14 +48,22 @@ int launch_bn_bwd_reduce(const float* g, const float* y, const float* scale, con
 int launch_bn_bwd_finalize(const float* partials, int nblk, int C, double count, const float* scale, const float* mean,
                            const float* invstd, float* dgamma, float* dbeta, double* coef, hipStream_t s,
                            const float* shift = nullptr, const float* beta = nullptr, float* coef_f = nullptr,
-                           const float* xs_partials = nullptr, int xs_n = 0, float* xs_out = nullptr);   // xs_*: a rider, xs_out[e] =
+                           const float* xs_partials = nullptr, int xs_n = 0, float* xs_out = nullptr,   // xs_*: a rider, xs_out[e] =
                            // the column sums of xs_partials[nblk][xs_n] (same row count) -- one launch less on the chain
+                           int frozen = 0);   // frozen (both finalizes): running-statistics BatchNorm, k1 = k0 = 0
 int launch_bn_bwd_finalize2(const float* pa, int na, const float* pb, int nb, int C, double count, const float* scale,
                             const float* mean, const float* invstd, float* dgamma, float* dbeta, double* coef, hipStream_t s,
-                            const float* shift = nullptr, const float* beta = nullptr, float* coef_f = nullptr);
+                            const float* shift = nullptr, const float* beta = nullptr, float* coef_f = nullptr, int frozen = 0);
 int launch_bn_bwd_apply(const float* g, const float* y, const float* scale, const float* shift, const double* coef,
                         int C, size_t npix, float* dy, hipStream_t s, const float* gp = nullptr, int H = 0, int W = 0);
 int launch_nbt_increment(long long* nbt, int n, hipStream_t s);
+
+// ---- adapt.hip ---- (fine-tuning a trained model, include/sifsr_adapt.h)
+// mean / invstd of all 17 layers from the running statistics: mean = running_mean, invstd = 1 / sqrtf(running_var + eps)
+int launch_bn_frozen_stats(const float* running, float eps, float* mean, float* invstd, hipStream_t s);
+// dX (B,2,H,W) of inbloc.bloc.0 under replicate padding from g, y (NHWC 16) and the float64 coefficients [scale | k1 | k0]
+int launch_conv_in_dgrad(const float* g, const float* y, const float* scale, const float* shift, const double* coef, const float* w,
+                         float* dx, int B, int H, int W, hipStream_t s);
 
 // ---- resample.hip ---- (all NHWC, C % 4 == 0; scale == nullptr => input used as stored)
 int launch_bnrelu_pool2(const float* y, const float* scale, const float* shift, float* out, int B, int H, int W, int C, hipStream_t s);

@@ -38,7 +38,11 @@ int sifsr_engine_forward(const float* x, float* sr, const float* params, float* 
                          size_t ws_floats, int B, int H, int W, int training, float momentum, float eps, hipStream_t s,
                          int bf16 = 0);
 int sifsr_engine_backward(const float* x, const float* dsr, const float* params, float* grads, float* ws,
-                          size_t ws_floats, int B, int H, int W, hipStream_t s, int bf16 = 0);
+                          size_t ws_floats, int B, int H, int W, hipStream_t s, int bf16 = 0, int frozen = 0, float* dx = nullptr);
+// frozen = 1: the workspace is that of sifsr_engine_forward_frozen (BatchNorm backward with constant statistics); dx != nullptr:
+// also the gradient with respect to the network input, (B,2,H,W).  Both fp32 only.
+int sifsr_engine_forward_frozen(const float* x, float* sr, const float* params, const float* running, float* ws, size_t ws_floats,
+                                int B, int H, int W, float eps, hipStream_t s);
 int sifsr_engine_set_wgrad_stream(int on);   // 1 / 0: weight gradients on their own stream or not; -1: SIFSR_WGRAD_STREAM / default (on)
 int sifsr_engine_profile_select(int layer, int phase);
 int sifsr_engine_profile_add(int layer, int phase);

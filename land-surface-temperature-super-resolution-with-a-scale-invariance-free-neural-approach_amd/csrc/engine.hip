@@ -183,6 +183,7 @@ struct Ctx {
   int B, H, W;
   hipStream_t s;
   int bf16 = 0;                     // 1: bf16 MFMA operands (config 5)
+  int frozen = 0;                   // backward: 1 = running-statistics BatchNorm (sifsr_engine_forward_frozen left the workspace)
   // backward only
   float* grads = nullptr;
   struct BwdState* bwd = nullptr;   // what the schedule accumulates while it is enqueued (below)
@@ -396,13 +397,13 @@ int bn_unit_bwd(const Ctx& c, int l, const float* gp = nullptr, int fused_stats 
     if (gp != nullptr) return SIFSR_ERR_ARG;
     return launch_bn_bwd_finalize2(c.f(c.lay.partials), fused_stats, c.f(c.lay.bpart), border_rows >= 0 ? border_rows : dgrad_border_waves(c.B, lh, lw, 16),
                                    L.cout, (double)npix, c.scale(l), c.mean(l), c.invstd(l), dgamma, dbeta, c.coef(), c.s, c.shift(l),
-                                   c.params + L.beta_off, c.coef_f(l));
+                                   c.params + L.beta_off, c.coef_f(l), c.frozen);
   }
   const int nblk = bn_bwd_reduce_blocks(npix);
   SIFSR_TRY(launch_bn_bwd_reduce(c.g(l), c.y(l), c.scale(l), c.shift(l), c.mean(l), c.invstd(l), L.cout, npix, c.f(c.lay.partials), nblk,
                                  c.s, gp, lh, lw, (gp && writeback) ? c.g(l) : nullptr));
   return launch_bn_bwd_finalize(c.f(c.lay.partials), nblk, L.cout, (double)npix, c.scale(l), c.mean(l), c.invstd(l), dgamma, dbeta,
-                                c.coef(), c.s, c.shift(l), c.params + L.beta_off, c.coef_f(l));
+                                c.coef(), c.s, c.shift(l), c.params + L.beta_off, c.coef_f(l), nullptr, 0, nullptr, c.frozen);
 }
 
 // SIFSR_WGRAD_WINO (switches.h): the Winograd-domain weight-gradient kernels for a layer with cout output channels?
@@ -638,15 +639,30 @@ int sifsr_engine_forward(const float* x, float* sr, const float* params, float* 
   return SIFSR_OK;
 }
 
+// Running-statistics forward that a backward can follow (fine-tuning with frozen BatchNorm): the eval-mode
+// schedule above -- same launches, same bits in sr -- in the TRAINING workspace, plus mean / invstd of every layer from the
+// running statistics, which the backward's reductions read.  `running` is only read.
+int sifsr_engine_forward_frozen(const float* x, float* sr, const float* params, const float* running, float* ws, size_t ws_floats,
+                                int B, int H, int W, float eps, hipStream_t s) {
+  if (!running || !ws) return SIFSR_ERR_ARG;
+  WsLayout lay;
+  SIFSR_TRY(sifsr_layout(B, H, W, 1, &lay));
+  if (ws_floats < lay.total) return SIFSR_ERR_WORKSPACE;
+  SIFSR_TRY(sifsr_engine_forward(x, sr, params, const_cast<float*>(running), nullptr, ws, ws_floats, B, H, W, 0, 0.f, eps, s, 0));
+  return launch_bn_frozen_stats(running, eps, ws + lay.mean, ws + lay.invstd, s);
+}
+
 // ---------------------------------------------------------------------------------------------
 // backward (requires the workspace of the matching training-mode forward)
 // ---------------------------------------------------------------------------------------------
 int sifsr_engine_backward(const float* x, const float* dsr, const float* params, float* grads, float* ws,
-                          size_t ws_floats, int B, int H, int W, hipStream_t s, int bf16) {
+                          size_t ws_floats, int B, int H, int W, hipStream_t s, int bf16, int frozen, float* dx) {
   if (!x || !dsr || !params || !grads || !ws) return SIFSR_ERR_ARG;
   Ctx c{sifsr_net(), WsLayout(), ws, params, B, H, W, s};
   if (bf16 < 0 || bf16 > 1) return SIFSR_ERR_ARG;
+  if ((frozen != 0 || dx != nullptr) && bf16 != 0) return SIFSR_ERR_ARG;   // both are fp32 only
   c.bf16 = bf16;
+  c.frozen = frozen != 0;
   const HalfStorageScope storage(bf16 == 1);
   SIFSR_TRY(sifsr_layout(B, H, W, 1, &c.lay));
   if (ws_floats < c.lay.total) return SIFSR_ERR_WORKSPACE;
@@ -666,7 +682,8 @@ int sifsr_engine_backward(const float* x, const float* dsr, const float* params,
   // now; D needs dz of inbloc.bloc.0, which the fused kernel of inbloc.bloc.3 stores in place of g.  One 16-channel tensor less to
   // read (the D pass: 75 us against 136 us for the fused head kernel, stand-alone), but the Gram kernel costs 93 us of vector
   // issue beside the chain's first kernels: 10,390 against 10,420 patches/s on the step (same device, interleaved) -- not adopted.
-  const bool head_linear = sw.head_linear != 0 && bwd16_usable(c, L_IN3, src_act(c, L_IN0));
+  // (off whenever the input gradient is asked for: conv_in_dgrad reads g of inbloc.bloc.0, and this form keeps dz in its place)
+  const bool head_linear = sw.head_linear != 0 && dx == nullptr && bwd16_usable(c, L_IN3, src_act(c, L_IN0));
   if (head_linear) {
     hipStream_t gs = s;
     if (c.side != nullptr) {
@@ -691,7 +708,7 @@ int sifsr_engine_backward(const float* x, const float* dsr, const float* params,
     if (grads + nt.out_b_off != grads + nt.out_w_off + 144) return SIFSR_ERR_ARG;
     SIFSR_TRY(launch_bn_bwd_finalize(c.f(w.partials), nblk, 16, (double)w.npix[0], c.scale(L_U3B), c.mean(L_U3B), c.invstd(L_U3B),
                                      grads + L.gamma_off, grads + L.beta_off, c.coef(), s, c.shift(L_U3B), params + L.beta_off,
-                                     c.coef_f(L_U3B), c.f(w.slabs), 145, grads + nt.out_w_off));   // (+ outlay dW / db)
+                                     c.coef_f(L_U3B), c.f(w.slabs), 145, grads + nt.out_w_off, c.frozen));   // (+ outlay dW / db)
     if (!tail_in_bwd16)
       SIFSR_TRY(launch_tail_bwd_apply(c.y(L_U3B), c.scale(L_U3B), c.shift(L_U3B), c.coef(), dsr, params + nt.out_w_off, c.g(L_U3B),
                                       B, H, W, s));
@@ -776,7 +793,8 @@ int sifsr_engine_backward(const float* x, const float* dsr, const float* params,
       SIFSR_TRY(launch_bn_bwd_reduce(c.g(L_IN0), c.y(L_IN0), c.scale(L_IN0), c.shift(L_IN0), c.mean(L_IN0), c.invstd(L_IN0), 16, npix,
                                      c.f(w.partials), nblk_r, s));
       SIFSR_TRY(launch_bn_bwd_finalize(c.f(w.partials), nblk_r, 16, (double)npix, c.scale(L_IN0), c.mean(L_IN0), c.invstd(L_IN0),
-                                       grads + L.gamma_off, grads + L.beta_off, c.coef(), s));
+                                       grads + L.gamma_off, grads + L.beta_off, c.coef(), s, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
+                                       c.frozen));
     }
     int nblk = B * ((H + 15) / 16) * ((W + 15) / 16);
     if (head_linear) {      // g[L_IN0] holds dz
@@ -790,6 +808,9 @@ int sifsr_engine_backward(const float* x, const float* dsr, const float* params,
       SIFSR_TRY(launch_conv_in_wgrad_fused(x, c.g(L_IN0), c.y(L_IN0), c.scale(L_IN0), c.shift(L_IN0), c.coef(), c.f(w.slabs), nblk,
                                            grads + L.w_off, B, H, W, s));
     }
+    // the network's input gradient (adapt.hip): dy(L_IN0) formed once more from (g, y) and the float64 coefficients above
+    if (dx != nullptr)
+      SIFSR_TRY(launch_conv_in_dgrad(c.g(L_IN0), c.y(L_IN0), c.scale(L_IN0), c.shift(L_IN0), c.coef(), params + L.w_off, dx, B, H, W, s));
   }
   if (c.side != nullptr) {   // hand the second stream's work back to the caller's stream
     SIFSR_TRY(lane_guard.join());

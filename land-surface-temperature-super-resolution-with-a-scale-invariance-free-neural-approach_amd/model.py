@@ -82,6 +82,10 @@ class _ModelFn(torch.autograd.Function):
         flat_p, flat_r, flat_n = module._flat_state(x.device)
         training = bool(module.training)
         need_bwd = training and any(ctx.needs_input_grad)   # grad mode is off inside forward(); this is the caller's
+        need_dx = need_bwd and ctx.needs_input_grad[1]      # x.requires_grad: the backward also returns dL/dx (sifsr_adapt.h)
+        # bn_frozen (fine-tuning): train() mode with the running statistics in the forward AND the backward.
+        # getattr: pickles from before the attribute existed.  Without a backward this is the eval-mode forward itself.
+        frozen = training and bool(getattr(module, "bn_frozen", False))
         if torch.cuda.is_current_stream_capturing():
             # a still-alive autograd graph of an EARLIER, un-captured step keeps the parameters'
             # AccumulateGrad nodes (bound to the stream they were made on) alive; the captured backward would make torch
@@ -104,9 +108,16 @@ class _ModelFn(torch.autograd.Function):
         compute = _COMPUTE_MODES.get(getattr(module, "compute_dtype", "fp32"))
         if compute is None:
             raise _lib.SifsrError(f"compute_dtype must be one of {sorted(_COMPUTE_MODES)}")
-        _lib.call("sifsr_model_forward_ex", x, sr, flat_p, flat_r, flat_n, ws, ws_bytes, B, H, W,
-                  1 if training else 0, bn[0], bn[1], compute, _lib.stream_ptr(x.device))
+        if compute != 0 and (frozen or need_dx):
+            raise _lib.SifsrError("bn_frozen and the input gradient (x.requires_grad) are fp32 only; set compute_dtype='fp32'")
+        if frozen and need_bwd:
+            _lib.call("sifsra_model_forward", x, sr, flat_p, flat_r, ws, ws_bytes, B, H, W, bn[1], _lib.stream_ptr(x.device))
+        else:
+            _lib.call("sifsr_model_forward_ex", x, sr, flat_p, flat_r, flat_n, ws, ws_bytes, B, H, W,
+                      1 if training and not frozen else 0, bn[0], bn[1], compute, _lib.stream_ptr(x.device))
         ctx.compute = compute
+        ctx.frozen = frozen
+        ctx.need_dx = need_dx
         ctx.module = module
         ctx.can_bwd = need_bwd
         ctx.training = training
@@ -132,13 +143,18 @@ class _ModelFn(torch.autograd.Function):
         dsr = dsr.contiguous()
         flat_p, _, _ = module._flat_state(dsr.device)
         grads = torch.empty_like(flat_p)
-        _lib.call("sifsr_model_backward_ex", ctx.x, dsr, flat_p, grads, ctx.ws, ctx.ws.numel(), B, H, W, ctx.compute,
-                  _lib.stream_ptr(dsr.device))
+        dx = torch.empty_like(ctx.x) if ctx.need_dx else None
+        if ctx.frozen or ctx.need_dx:
+            _lib.call("sifsra_model_backward", ctx.x, dsr, flat_p, grads, dx, ctx.ws, ctx.ws.numel(), B, H, W,
+                      1 if ctx.frozen else 0, _lib.stream_ptr(dsr.device))
+        else:
+            _lib.call("sifsr_model_backward_ex", ctx.x, dsr, flat_p, grads, ctx.ws, ctx.ws.numel(), B, H, W, ctx.compute,
+                      _lib.stream_ptr(dsr.device))
         ctx.ws = None
         ctx.x = None
         module._last_flat_grad = grads
         outs = [grads[o:o + n].view(s) for (o, n, s) in module._param_slices]
-        return (None, None, *outs)
+        return (None, dx, *outs)
 
 
 class ModelB_2(nn.Module):
@@ -170,6 +186,9 @@ class ModelB_2(nn.Module):
         # not in the reference: 'fp32' (default, the parity path) or 'bf16' = BASELINE.json config 5, bf16 MFMA operands in
         # the 3x3 convs (fp32 accumulation / storage / parameters) -- set the attribute, nothing else changes
         self.compute_dtype = "fp32"
+        # not in the reference: True = in train() mode BatchNorm normalises by its running statistics, forward and backward, and
+        # leaves its buffers alone (fine-tuning a trained model: sifsr.adapt, include/sifsr_adapt.h); eval() is unaffected
+        self.bn_frozen = False
         d, uf = downchannels, self.upfactor
         self.inbloc = _Bloc(in_channels, d[0], None, padding_mode)          # model.py:596
         self.db1 = _Down(d[0], d[1], padding_mode)                           # :597
