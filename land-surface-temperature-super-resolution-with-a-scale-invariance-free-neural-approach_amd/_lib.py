@@ -1,20 +1,10 @@
 """ctypes binding of libsifsr_hip.so.
 
-The signatures are parsed from ``include/sifsr_hip.h`` -- the header is the single source of truth
-for the C ABI, and ``tests/test_capi_symbols.py`` checks that the library exports every declared
-symbol -- and from its extensions ``include/sifsr_mosaic.h`` (prefix ``sifsrx_``, same declaration style,
-gated by ``tests/test_mosaic_host.py``), ``include/sifsr_baselines.h`` (prefix ``sifsrb_``, gated by
-``tests/test_baselines_host.py``), ``include/sifsr_products.h`` (prefix ``sifsrp_``, gated by
-``tests/test_products_host.py``), ``include/sifsr_gaps.h`` (prefix ``sifsrg_``, gated by
-``tests/test_gaps_host.py``), ``include/sifsr_masked.h`` (prefix ``sifsrm_``, gated by
-``tests/test_masked_host.py``), ``include/sifsr_scores.h`` (prefix ``sifsrv_``, gated by
-``tests/test_scores_host.py``), ``include/sifsr_lpips.h`` (prefix ``sifsrl_``, gated by
-``tests/test_lpips_host.py``), ``include/sifsr_conserve.h`` (prefix ``sifsrk_``, gated by
-``tests/test_conserve_host.py``), ``include/sifsr_dms.h`` (prefix ``sifsrd_``, gated by
-``tests/test_dms_host.py``), ``include/sifsr_spectra.h`` (prefix ``sifsrf_``, gated by
-``tests/test_spectra_host.py``), ``include/sifsr_degrade.h`` (prefix ``sifsrs_``, gated by
-``tests/test_degrade_host.py``) and ``include/sifsr_adapt.h`` (prefix ``sifsra_``, gated by
-``tests/test_adapt_host.py``).  There is NO fallback: if the library is missing or a call fails, we raise.
+The signatures are parsed from the headers under ``include/`` -- the headers are the single source of truth for the C ABI.
+``FAMILIES`` below is the one table of them: ``include/sifsr_hip.h`` (``core``, prefix ``sifsr_``) and its extensions, one
+header and one symbol prefix each.  ``tests/test_capi_gate.py`` checks, for every row, that the library exports exactly the
+declared symbols and that every writing entry point has memory-contract cases.  There is NO fallback: if the library is
+missing, of another ABI version, or a call fails, we raise.
 """
 from __future__ import annotations
 
@@ -26,19 +16,37 @@ import torch  # noqa: F401  (must be imported first: the library binds to the li
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
-HEADER = os.path.join(_ROOT, "include", "sifsr_hip.h")
-EXTENSION_HEADER = os.path.join(_ROOT, "include", "sifsr_mosaic.h")
-BASELINES_HEADER = os.path.join(_ROOT, "include", "sifsr_baselines.h")
-PRODUCTS_HEADER = os.path.join(_ROOT, "include", "sifsr_products.h")
-GAPS_HEADER = os.path.join(_ROOT, "include", "sifsr_gaps.h")
-MASKED_HEADER = os.path.join(_ROOT, "include", "sifsr_masked.h")
-SCORES_HEADER = os.path.join(_ROOT, "include", "sifsr_scores.h")
-LPIPS_HEADER = os.path.join(_ROOT, "include", "sifsr_lpips.h")
-CONSERVE_HEADER = os.path.join(_ROOT, "include", "sifsr_conserve.h")
-DMS_HEADER = os.path.join(_ROOT, "include", "sifsr_dms.h")
-SPECTRA_HEADER = os.path.join(_ROOT, "include", "sifsr_spectra.h")
-DEGRADE_HEADER = os.path.join(_ROOT, "include", "sifsr_degrade.h")
-ADAPT_HEADER = os.path.join(_ROOT, "include", "sifsr_adapt.h")
+# The C ABI: family -> (header under include/, symbol prefix).  `core` is the main header; every other row is an extension with
+# the same declaration style.  lib() binds them all; tests/test_capi_gate.py gates each row against the built library.
+FAMILIES = {
+    "core": ("sifsr_hip.h", "sifsr_"),
+    "mosaic": ("sifsr_mosaic.h", "sifsrx_"),
+    "baselines": ("sifsr_baselines.h", "sifsrb_"),
+    "products": ("sifsr_products.h", "sifsrp_"),
+    "gaps": ("sifsr_gaps.h", "sifsrg_"),
+    "masked": ("sifsr_masked.h", "sifsrm_"),
+    "scores": ("sifsr_scores.h", "sifsrv_"),
+    "lpips": ("sifsr_lpips.h", "sifsrl_"),
+    "conserve": ("sifsr_conserve.h", "sifsrk_"),
+    "dms": ("sifsr_dms.h", "sifsrd_"),
+    "spectra": ("sifsr_spectra.h", "sifsrf_"),
+    "degrade": ("sifsr_degrade.h", "sifsrs_"),
+    "adapt": ("sifsr_adapt.h", "sifsra_"),
+}
+ABI_VERSION = 3
+# the entry points whose int return is a count, not a status: call() raises on a non-zero int from every other one
+COUNT_RETURNING = frozenset({
+    "sifsr_abi_version", "sifsr_num_params", "sifsr_num_running", "sifsr_layer_table", "sifsr_model_workspace_regions",
+    "sifsr_conv3x3_stat_blocks", "sifsr_conv3x3_stat_blocks_wino", "sifsr_conv3x3_bwd16_stat_rows", "sifsr_conv_in_stat_blocks",
+    "sifsr_up2x_bwd_stat_rows", "sifsr_huber_partial_blocks", "sifsr_profile_add", "sifsrx_tile_count", "sifsrx_tile_origin",
+})
+
+
+def header_path(family: str = "core") -> str:
+    return os.path.join(_ROOT, "include", FAMILIES[family][0])
+
+
+HEADER = header_path()
 # SIFSR_LIB: another build of the same C ABI (same-device A/B of kernel variants, tools/ab/); default: the in-tree library
 LIB_PATH = os.environ.get("SIFSR_LIB") or os.path.join(_HERE, "libsifsr_hip.so")
 
@@ -51,8 +59,17 @@ class SifsrError(RuntimeError):
     pass
 
 
+class Arg(tuple):
+    """(name, ctype) as lib() binds it, plus what the declaration says of the memory: .pointer and .const"""
+
+    def __new__(cls, name, ctype, pointer, const):
+        self = super().__new__(cls, (name, ctype))
+        self.pointer, self.const = pointer, const
+        return self
+
+
 def parse_header(path: str = HEADER):
-    """-> {name: (restype, [(argname, ctype)])} for every SIFSR_API declaration."""
+    """-> {name: (restype, [Arg(argname, ctype)])} for every SIFSR_API declaration."""
     text = open(path).read()
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     decls = {}
@@ -64,12 +81,30 @@ def parse_header(path: str = HEADER):
                 a = " ".join(a.split())
                 mm = re.match(r"(.+?)\s*(\w+)$", a)
                 typ, an = mm.group(1).strip(), mm.group(2)
-                if "*" in typ:
-                    parsed.append((an, ctypes.c_void_p))
-                else:
-                    parsed.append((an, _CTYPES[typ.replace("const ", "")]))
+                pointer, const = "*" in typ, "const" in typ
+                parsed.append(Arg(an, ctypes.c_void_p if pointer else _CTYPES[typ.replace("const ", "")], pointer, const))
         decls[name] = (_CTYPES[ret], parsed)
     return decls
+
+
+def declared(family: str = "core"):
+    """The sorted names the family's header declares."""
+    return sorted(parse_header(header_path(family)))
+
+
+def declared_symbols():
+    return declared()
+
+
+def writers(family: str = "core"):
+    """-> {name: [non-const pointer argument names]} of the family's entry points that have any: what a call may write through.
+    The `stream` handle is not memory."""
+    out = {}
+    for name, (_, args) in parse_header(header_path(family)).items():
+        ptrs = [a[0] for a in args if a.pointer and not a.const and a[0] != "stream"]
+        if ptrs:
+            out[name] = ptrs
+    return out
 
 
 _lib = None
@@ -77,7 +112,7 @@ _decls = None
 
 
 def lib():
-    """Load (once) and return the ctypes handle; raises SifsrError if the HIP library is absent."""
+    """Load (once) and return the ctypes handle; raises SifsrError if the HIP library is absent or of another ABI version."""
     global _lib, _decls
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -85,81 +120,19 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        _decls = {**parse_header(), **parse_header(EXTENSION_HEADER), **parse_header(BASELINES_HEADER),
-                  **parse_header(PRODUCTS_HEADER), **parse_header(GAPS_HEADER), **parse_header(MASKED_HEADER),
-                  **parse_header(SCORES_HEADER), **parse_header(LPIPS_HEADER), **parse_header(CONSERVE_HEADER),
-                  **parse_header(DMS_HEADER), **parse_header(SPECTRA_HEADER), **parse_header(DEGRADE_HEADER),
-                  **parse_header(ADAPT_HEADER)}
-        for name, (ret, args) in _decls.items():
+        decls = {}
+        for family in FAMILIES:
+            decls.update(parse_header(header_path(family)))
+        for name, (ret, args) in decls.items():
             fn = getattr(handle, name)     # AttributeError if the library lacks a declared symbol
             fn.restype = ret
             fn.argtypes = [t for _, t in args]
-        _lib = handle
+        got = handle.sifsr_abi_version()
+        if got != ABI_VERSION:
+            via = " (given by SIFSR_LIB)" if os.environ.get("SIFSR_LIB") else ""
+            raise SifsrError(f"{LIB_PATH}{via} has ABI version {got}, this binding needs {ABI_VERSION}: rebuild the library")
+        _lib, _decls = handle, decls
     return _lib
-
-
-def declared_symbols():
-    return sorted(parse_header().keys())
-
-
-def declared_extension_symbols():
-    """The names ``include/sifsr_mosaic.h`` declares (``sifsrx_*``); ``declared_symbols`` stays the main header's."""
-    return sorted(parse_header(EXTENSION_HEADER).keys())
-
-
-def declared_baseline_symbols():
-    """The names ``include/sifsr_baselines.h`` declares (``sifsrb_*``)."""
-    return sorted(parse_header(BASELINES_HEADER).keys())
-
-
-def declared_product_symbols():
-    """The names ``include/sifsr_products.h`` declares (``sifsrp_*``)."""
-    return sorted(parse_header(PRODUCTS_HEADER).keys())
-
-
-def declared_gap_symbols():
-    """The names ``include/sifsr_gaps.h`` declares (``sifsrg_*``)."""
-    return sorted(parse_header(GAPS_HEADER).keys())
-
-
-def declared_masked_symbols():
-    """The names ``include/sifsr_masked.h`` declares (``sifsrm_*``)."""
-    return sorted(parse_header(MASKED_HEADER).keys())
-
-
-def declared_score_symbols():
-    """The names ``include/sifsr_scores.h`` declares (``sifsrv_*``)."""
-    return sorted(parse_header(SCORES_HEADER).keys())
-
-
-def declared_lpips_symbols():
-    """The names ``include/sifsr_lpips.h`` declares (``sifsrl_*``)."""
-    return sorted(parse_header(LPIPS_HEADER).keys())
-
-
-def declared_conserve_symbols():
-    """The names ``include/sifsr_conserve.h`` declares (``sifsrk_*``)."""
-    return sorted(parse_header(CONSERVE_HEADER).keys())
-
-
-def declared_dms_symbols():
-    """The names ``include/sifsr_dms.h`` declares (``sifsrd_*``)."""
-    return sorted(parse_header(DMS_HEADER).keys())
-
-
-def declared_spectra_symbols():
-    """The names ``include/sifsr_spectra.h`` declares (``sifsrf_*``)."""
-    return sorted(parse_header(SPECTRA_HEADER).keys())
-
-
-def declared_degrade_symbols():
-    """The names ``include/sifsr_degrade.h`` declares (``sifsrs_*``)."""
-    return sorted(parse_header(DEGRADE_HEADER).keys())
-
-
-def declared_adapt_symbols():
-    """The names ``include/sifsr_adapt.h`` declares (``sifsra_*``)."""
-    return sorted(parse_header(ADAPT_HEADER).keys())
 
 
 def _conv(v):
@@ -174,7 +147,7 @@ def call(name: str, *args):
     """Call a C-ABI function; tensors are passed as device pointers.  Raises on a non-zero status."""
     fn = getattr(lib(), name)
     rc = fn(*[_conv(a) for a in args])
-    if fn.restype is ctypes.c_int and rc != 0 and not name.startswith(("sifsr_abi", "sifsr_num", "sifsr_layer", "sifsr_huber_partial", "sifsr_model_workspace_regions", "sifsr_conv3x3_stat", "sifsr_conv_in_stat", "sifsr_conv3x3_bwd16_stat", "sifsr_profile_add", "sifsr_up2x_bwd_stat", "sifsrx_tile_")):
+    if fn.restype is ctypes.c_int and rc != 0 and name not in COUNT_RETURNING:
         raise SifsrError(f"{name} failed with status {rc}")
     return rc
 

@@ -34,7 +34,7 @@ def build(force=False, verbose=False, extra=(), lib=None, obj_dir=None, csrc=Non
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     inc = os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include")
-    hdrs += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")]      # sifsr_hip.h and its extensions (sifsr_mosaic.h, sifsr_baselines.h, sifsr_products.h, sifsr_gaps.h, sifsr_masked.h, sifsr_scores.h, sifsr_lpips.h, sifsr_conserve.h, sifsr_dms.h, sifsr_spectra.h, sifsr_degrade.h, sifsr_adapt.h)
+    hdrs += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")]      # sifsr_hip.h and its extensions (the rows of _lib.FAMILIES)
     os.makedirs(OBJ_, exist_ok=True)
     jobs = []
     for f in srcs:

@@ -8,7 +8,7 @@ tests/adapt_reference.py.
   * no cross-sample coupling in frozen mode; the second stream changes no bit,
   * sifsra_conv_in_dgrad at edge shapes: corners, edges and interior each within 1e-4, two runs bit-equal,
   * the memory contract of the four writers in the guarded, poisoned arena of tests/memcheck.py (CONTRACT is the table
-    tests/test_adapt_host.py checks against the header),
+    tests/test_capi_gate.py checks against the header),
   * tile_targets bit-equal to the restatement; adapt_granule bit-equal to the loop written out here, its first step against the
     float64 oracle; the frozen step captured into a hipGraph; the refusals."""
 import numpy as np
@@ -19,30 +19,14 @@ from oracle import checks as C
 from oracle import sif_oracle as O
 from tests import adapt_reference as A
 from tests.conftest import rel_err
-from tests.memcheck import Arena, Plain, bit_equal, same_under_all_poisons
+from tests.contract import L, S, run_contract, sifsr  # noqa: F401  (L and sifsr are the fixtures)
+from tests.memcheck import bit_equal
 from tests.test_model_gpu import TOL, make_model, read_masks
 
 pytestmark = pytest.mark.gpu
 MEAN, STD = A.MEAN, A.STD
 ALPHA, GAMMA = 0.5, -0.25
 F32, F64, U8, I32, I64 = torch.float32, torch.float64, torch.uint8, torch.int32, torch.int64
-
-
-@pytest.fixture(scope="module")
-def sifsr():
-    import sifsr as pkg
-    assert torch.cuda.is_available()
-    return pkg
-
-
-@pytest.fixture(scope="module")
-def L(sifsr):
-    from sifsr import _lib
-    return _lib
-
-
-def S():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def flat_params(sd):
@@ -306,24 +290,12 @@ CONTRACT = {"sifsra_model_forward": [model_case("forward"), model_case("forward"
 CASES = [(name, i) for name, cases in CONTRACT.items() for i in range(len(cases))]
 
 
-def _execute(L, A_, name, idx):
-    call, outs = CONTRACT[name][idx](A_, L)
-    torch.cuda.synchronize()
-    call()
-    torch.cuda.synchronize()
-    A_.check()                                          # no guard byte and no const input (`running` included) changed
-    return {n: v.clone() for n, v in outs.items()}
-
-
 @pytest.mark.parametrize("name,idx", CASES, ids=[f"{n[7:]}-{i}" for n, i in CASES])
 def test_memory_contract(L, name, idx):
     """every output written in full and nowhere else -- NaN-free under the NaN poison, bit-identical under every poison of the
     outputs AND the workspace (no workspace byte is read before it is written) --, const inputs untouched, and the same bits on
     ordinary allocations."""
-    first = same_under_all_poisons(lambda p: _execute(L, Arena("cuda", poison=p, capacity=96 << 20), name, idx))
-    plain = _execute(L, Plain("cuda"), name, idx)
-    for n, v in first.items():
-        assert bit_equal(v, plain[n]), f"{n}: the arena run and the ordinary-allocation run differ"
+    run_contract(L, lambda k: CONTRACT[name][idx](k.A, k.L), seed=0, capacity=96 << 20)     # (the cases are not seeded)
 
 
 # ---- tile targets ----------------------------------------------------------------------------------------------------------------

@@ -1,8 +1,7 @@
 """CPU: fine-tuning a trained model -- what can be held without a GPU.
 
-  * the gate of include/sifsr_adapt.h, restated from tests/test_masked_host.py for the `sifsra_` entry points: the exported
-    symbols are exactly the declared ones, none falls under another header, every entry point that can write through a pointer
-    has a memory-contract case in tests/test_adapt_gpu.py,
+  * the pins of include/sifsr_adapt.h for the `sifsra_` entry points (the gate itself is tests/test_capi_gate.py): the declared
+    names, every entry point that can write through a pointer has a memory-contract case in tests/test_adapt_gpu.py,
   * workspace sizes and the error codes that are found before anything is launched,
   * the restatements of tests/adapt_reference.py: the frozen network with every mask taken from its own forward IS plain torch
     eval-mode autograd; the operator-level input gradient against a written-out scatter; the tile targets against gaps_reference
@@ -12,7 +11,6 @@ import ctypes
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,57 +19,22 @@ import torch
 from oracle import sif_oracle as O
 from tests import adapt_reference as A
 from tests import gaps_reference as G
+from tests.capi_host import L  # noqa: F401  (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["sifsra_conv_in_dgrad", "sifsra_model_backward", "sifsra_model_forward", "sifsra_model_workspace_bytes", "sifsra_tile_targets"]
 
 
-@pytest.fixture(scope="module")
-def L():
-    import sifsr  # noqa: F401
-    from sifsr import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib
-
-
-def _declarations():
-    """{name: [non-const pointer parameters]} of include/sifsr_adapt.h"""
-    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "sifsr_adapt.h")).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"SIFSR_API\s+[\w\s]+?\s+(\w+)\s*\(([^)]*)\)\s*;", text):
-        args = [" ".join(a.split()) for a in m.group(2).split(",")]
-        out[m.group(1)] = [a.split()[-1].lstrip("*") for a in args if "*" in a and not a.startswith("const ") and a.split()[-1] != "stream"]
-    return out
-
-
-# ---- 1. the gate ---------------------------------------------------------------------------------------------------------------
-def test_exported_adapt_symbols_are_the_declared_ones(L):
-    names = L.declared_adapt_symbols()
-    assert set(names) == set(_declarations()) and names == NAMES
-    assert all(n.startswith("sifsra_") and "sifsr_" not in n for n in names)
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("sifsra_")}
-    assert exported == set(names), exported ^ set(names)
-    others = set()
-    for fn in (L.declared_symbols, L.declared_extension_symbols, L.declared_baseline_symbols, L.declared_product_symbols,
-               L.declared_gap_symbols, L.declared_masked_symbols, L.declared_score_symbols, L.declared_lpips_symbols,
-               L.declared_conserve_symbols, L.declared_dms_symbols, L.declared_spectra_symbols, L.declared_degrade_symbols):
-        others |= set(fn())
-    assert not set(names) & others
-    assert all(hasattr(L.lib(), n) for n in names)
-    assert L.call("sifsr_abi_version") == 3
-
-
+# ---- 1. the pins of include/sifsr_adapt.h (the gate itself is tests/test_capi_gate.py) ------------------------------------------
 def test_every_writing_adapt_entry_point_has_a_contract_case(L):
     from tests import test_adapt_gpu as T
-    writers = {n: p for n, p in _declarations().items() if p}
+    names, writers = L.declared("adapt"), L.writers("adapt")
+    assert names == NAMES
     assert writers == {"sifsra_model_forward": ["sr", "workspace"],
                        "sifsra_model_backward": ["grads", "dx", "workspace"],
                        "sifsra_conv_in_dgrad": ["dx"],
                        "sifsra_tile_targets": ["lst_out", "valid_out", "n_valid_out"]}
-    assert _declarations()["sifsra_model_workspace_bytes"] == []              # host only
+    assert "sifsra_model_workspace_bytes" not in writers                      # host only
     assert sorted(T.CONTRACT) == sorted(writers)
     assert len(T.CONTRACT["sifsra_model_backward"]) >= 2                       # with and without dx
 

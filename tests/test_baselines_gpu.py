@@ -8,7 +8,7 @@ AATPRK of the reference's utils.py:854-1606 on the device.
     the shapes where the tiling can go wrong,
   * batch rows bit-equal to single-image calls, the window fallback of AATPRK, the uncorrected border of the kriging methods,
   * the memory contract of every writing entry point in the guarded, poisoned arena of tests/memcheck.py (CONTRACT below is the
-    table tests/test_baselines_host.py checks against the header), and the argument errors.
+    table tests/test_capi_gate.py checks against the header), and the argument errors.
 
 Bounds.  1e-4 K: the arithmetic before the store is float64, the store rounds once to float32, whose spacing at 256..512 K is
 3.05e-5 K -- three of them.  1e-9 relative on the semivariogram: float64 sums of at most a few thousand terms of one sign.  Both
@@ -22,8 +22,8 @@ import pytest
 import torch
 
 from tests import baselines_reference as R
-from tests.memcheck import Arena, Plain, bit_equal, same_under_all_poisons
-from tests.test_memory_contract_gpu import K, S
+from tests.contract import L, S, run_contract, sifsr  # noqa: F401  (L and sifsr are the fixtures)
+from tests.memcheck import bit_equal
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,21 +34,9 @@ SHAPE_ERR, ARG_ERR = 1001, 1002
 
 
 @pytest.fixture(scope="module")
-def sifsr():
-    import sifsr as pkg
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return pkg
-
-
-@pytest.fixture(scope="module")
 def BL(sifsr):
     from sifsr import baselines
     return baselines
-
-
-@pytest.fixture(scope="module")
-def L(sifsr):
-    return sifsr._lib
 
 
 @pytest.fixture(scope="module")
@@ -349,24 +337,11 @@ CONTRACT = {
 CASES = [(name, i) for name, cases in CONTRACT.items() for i in range(len(cases))]
 
 
-def _execute(L, A, name, idx):
-    k = K(A, L, seed=sum(map(ord, name)) * 131 + idx)
-    call, outs = CONTRACT[name][idx](k)
-    torch.cuda.synchronize()
-    call()
-    torch.cuda.synchronize()
-    A.check()                                           # no guard byte and no const input changed
-    return {n: v.clone() for n, v in outs.items()}
-
-
 @pytest.mark.parametrize("name,idx", CASES, ids=[f"{n[7:]}-{i}" for n, i in CASES])
 def test_memory_contract(L, name, idx):
     """every output (and the semivariogram's scratch) fully written -- NaN-free under the NaN poison, bit-identical under every
     poison --, inputs untouched, nothing outside the buffers written, and the same bits on ordinary allocations."""
-    first = same_under_all_poisons(lambda p: _execute(L, Arena("cuda", poison=p, capacity=64 << 20), name, idx))
-    plain = _execute(L, Plain("cuda"), name, idx)
-    for n, v in first.items():
-        assert bit_equal(v, plain[n]), f"{n}: the arena run and the ordinary-allocation run differ"
+    run_contract(L, CONTRACT[name][idx], seed=sum(map(ord, name)) * 131 + idx, capacity=64 << 20)
 
 
 # ---- 7. errors ---------------------------------------------------------------------------------------------------------------

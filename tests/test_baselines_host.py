@@ -4,21 +4,19 @@
     the reference's own images and Gamma_coarse (tests/golden/golden_baselines_v1.npz) to 1e-9 when given the reference's fit 2,
   * sifsr.baselines' host side -- its own damped least squares and the kriging system -- fed the golden Gamma_coarse gives weights
     whose image, through the restatement, is within the project's parity bar (1e-4 of the image's maximum) of the reference's,
-  * the gate of include/sifsr_baselines.h, restated from tests/test_mosaic_host.py for the `sifsrb_` entry points: the exported
-    symbols are exactly the declared ones, none falls under the other two headers' export checks, every entry point that can write
-    through a pointer has a memory-contract case in tests/test_baselines_gpu.py,
+  * the pins of include/sifsr_baselines.h for the `sifsrb_` entry points (the gate itself is tests/test_capi_gate.py): the declared
+    names, every entry point that can write through a pointer has a memory-contract case in tests/test_baselines_gpu.py,
   * the drop-in names exist with the reference's signatures."""
 import ast
-import ctypes
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import baselines_reference as R
+from tests.capi_host import L  # noqa: F401  (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KRIGING = [(i, m) for i in (0, 1) for m in ("atprk", "aatprk")]
@@ -27,16 +25,6 @@ KRIGING = [(i, m) for i in (0, 1) for m in ("atprk", "aatprk")]
 @pytest.fixture(scope="module")
 def golden():
     return np.load(os.path.join(ROOT, "tests", "golden", "golden_baselines_v1.npz"))
-
-
-@pytest.fixture(scope="module")
-def L():
-    import sifsr  # noqa: F401
-    from sifsr import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib
 
 
 def _case(golden, i):
@@ -118,48 +106,13 @@ def test_host_fit_is_capped_and_refuses_a_bad_variogram():
     assert it <= 5                                                                                       # a straight line: no finite range
 
 
-# ---- the gate, restated for include/sifsr_baselines.h -----------------------------------------------------------------------
-def _declarations():
-    """{name: [non-const pointer argument names]} of every SIFSR_API declaration of the header, parsed as sifsr._lib.parse_header
-    does but keeping `const`; the `stream` handle is not memory."""
-    text = open(os.path.join(ROOT, "include", "sifsr_baselines.h")).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    out = {}
-    for m in re.finditer(r"SIFSR_API\s+([\w\s]+?)\s+(\w+)\s*\(([^)]*)\)\s*;", text):
-        ptrs = []
-        for a in m.group(3).split(","):
-            a = " ".join(a.split())
-            mm = re.match(r"(.+?)\s*(\w+)$", a)
-            if mm and "*" in mm.group(1) and "const" not in mm.group(1) and mm.group(2) != "stream":
-                ptrs.append(mm.group(2))
-        out[m.group(2)] = ptrs
-    return out
-
-
-def test_exported_baseline_symbols_are_the_declared_ones(L):
-    names = L.declared_baseline_symbols()
-    assert set(names) == set(_declarations()) and len(names) == 6
-    assert all(n.startswith("sifsrb_") and "sifsr_" not in n and not n.startswith("sifsrx_") for n in names)
-    handle = ctypes.CDLL(L.LIB_PATH)
-    assert not [n for n in names if not hasattr(handle, n)]
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("sifsrb_")}
-    assert exported == set(names), exported ^ set(names)
-    # the three headers do not overlap, the binding carries all of them, and the main ABI is the one it was
-    assert not set(names) & set(L.declared_symbols()) and not set(names) & set(L.declared_extension_symbols())
-    assert all(hasattr(L.lib(), n) for n in names)
-    assert L.call("sifsr_abi_version") == 3
-
-
+# ---- the pins of include/sifsr_baselines.h (the gate itself is tests/test_capi_gate.py) --------------------------------------
 def test_every_writing_baseline_entry_point_has_a_contract_case(L):
     from tests import test_baselines_gpu as T
-    writers = {n: p for n, p in _declarations().items() if p}
+    assert len(L.declared("baselines")) == 6
+    writers = L.writers("baselines")
     assert writers == {"sifsrb_linfit": ["fit"], "sifsrb_linfit_window": ["coef"], "sifsrb_residual": ["delta"],
                        "sifsrb_semivariogram": ["scratch", "gamma"], "sifsrb_sharpen": ["out"]}
-    missing = sorted(set(writers) - set(T.CONTRACT))
-    assert not missing, f"no memory-contract case for {missing}: add a row to CONTRACT in tests/test_baselines_gpu.py"
-    stale = sorted(set(T.CONTRACT) - set(writers))
-    assert not stale, f"CONTRACT rows for entry points the header does not declare as writers: {stale}"
     assert all(len(cases) >= 3 for cases in T.CONTRACT.values())
 
 

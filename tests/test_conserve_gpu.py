@@ -24,8 +24,8 @@ import torch
 
 from oracle import sif_oracle as O
 from tests import conserve_reference as R
-from tests.memcheck import Arena, Plain, bit_equal, same_under_all_poisons
-from tests.test_memory_contract_gpu import K, S
+from tests.contract import L, S, run_contract, sifsr  # noqa: F401  (L and sifsr are the fixtures)
+from tests.memcheck import bit_equal
 from tests.test_mosaic_gpu import STATS, _granule, _model
 
 pytestmark = pytest.mark.gpu
@@ -33,18 +33,6 @@ TOL = 2e-4
 SHAPE_ERR, ARG_ERR, WORKSPACE_ERR = 1001, 1002, 1003
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "golden_conserve_v1.npz")
-
-
-@pytest.fixture(scope="module")
-def sifsr():
-    import sifsr as pkg
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return pkg
-
-
-@pytest.fixture(scope="module")
-def L(sifsr):
-    return sifsr._lib
 
 
 def dev(a):
@@ -325,14 +313,7 @@ def conserve_case(i):
 CONTRACT = {"sifsrk_conserve": [conserve_case(i) for i in range(len(CONTRACT_SHAPES))]}
 
 
-def _execute(L, A, idx):
-    k = K(A, L, seed=977 + idx)
-    call, outs = CONTRACT["sifsrk_conserve"][idx](k)
-    torch.cuda.synchronize()
-    call()
-    torch.cuda.synchronize()
-    A.check()                                           # no guard byte and no const input changed
-    res = {n: v.clone() for n, v in outs.items()}
+def _as_bits(res):
     # NaN is data here (a NaN sr pixel keeps its bits; statistics of nothing are NaN): compare those by bits, keep the NaN check for r
     res["stats"] = res["stats"].view(torch.int64)
     if "out" in res:
@@ -345,10 +326,7 @@ def test_memory_contract(L, idx):
     """out, stats and r written in full and nowhere else -- bit-identical under every poison of the outputs and of the workspace, r
     NaN-free under the NaN poison --, const inputs untouched, nothing outside the buffers written, the same bits on ordinary
     allocations, and the result is the restatement's."""
-    first = same_under_all_poisons(lambda p: _execute(L, Arena("cuda", poison=p, capacity=64 << 20), idx))
-    plain = _execute(L, Plain("cuda"), idx)
-    for n, v in first.items():
-        assert bit_equal(v, plain[n]), f"{n}: the arena run and the ordinary-allocation run differ"
+    first = run_contract(L, CONTRACT["sifsrk_conserve"][idx], seed=977 + idx, capacity=64 << 20, view=_as_bits)
     h, w, n_iter, _, _ = CONTRACT_SHAPES[idx]
     sr, lst, mask = contract_inputs(idx)
     ro, rstats, rr, c, n = R.conserve_ref(sr, lst, mask, n_iter, relax=0.75)

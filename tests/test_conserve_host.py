@@ -8,34 +8,24 @@
   * convergence, recorded: on the golden cases the RMSE falls with every one of three steps (relax 1: to below a sixth after the
     first; relax 0.5: by at least a third per step), and the bias to below 0.02 K after the first step at relax 1.  The GPU test
     asserts the fall and nothing more,
-  * the gate of include/sifsr_conserve.h, restated from tests/test_scores_host.py for the `sifsrk_` entry points: the exported symbols
-    are exactly the declared ones, none falls under the other headers, the writing entry point has memory-contract cases in
-    tests/test_conserve_gpu.py, the workspace size and the error codes through the host-only paths,
+  * the pins of include/sifsr_conserve.h for the `sifsrk_` entry points (the gate itself is tests/test_capi_gate.py): the declared
+    names, the writing entry point has memory-contract cases in tests/test_conserve_gpu.py, the workspace size and the error codes
+    through the host-only paths,
   * the public names exist with the defaults that leave every existing call as it was."""
 import ctypes
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import conserve_reference as R
+from tests.capi_host import L  # noqa: F401  (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "golden_conserve_v1.npz")
-
-
-@pytest.fixture(scope="module")
-def L():
-    import sifsr  # noqa: F401
-    from sifsr import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib
 
 
 @pytest.fixture(scope="module")
@@ -157,46 +147,12 @@ def test_convergence_recorded(gold):
         assert np.all(rows[:, 3] >= rmse)
 
 
-# ---- 2. the gate, restated for include/sifsr_conserve.h ----------------------------------------------------------------------------
-def _declarations():
-    """{name: [non-const pointer argument names]} of every SIFSR_API declaration of the header; the `stream` handle is not memory."""
-    text = open(os.path.join(ROOT, "include", "sifsr_conserve.h")).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    out = {}
-    for m in re.finditer(r"SIFSR_API\s+([\w\s]+?)\s+(\w+)\s*\(([^)]*)\)\s*;", text):
-        ptrs = []
-        for a in m.group(3).split(","):
-            a = " ".join(a.split())
-            mm = re.match(r"(.+?)\s*(\w+)$", a)
-            if mm and "*" in mm.group(1) and "const" not in mm.group(1) and mm.group(2) != "stream":
-                ptrs.append(mm.group(2))
-        out[m.group(2)] = ptrs
-    return out
-
-
-def test_exported_conserve_symbols_are_the_declared_ones(L):
-    names = L.declared_conserve_symbols()
-    assert set(names) == set(_declarations())
-    assert names == ["sifsrk_conserve", "sifsrk_workspace_bytes"]
-    assert all(n.startswith("sifsrk_") and "sifsr_" not in n for n in names)
-    handle = ctypes.CDLL(L.LIB_PATH)
-    assert not [n for n in names if not hasattr(handle, n)]
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("sifsrk_")}
-    assert exported == set(names), exported ^ set(names)
-    others = (set(L.declared_symbols()) | set(L.declared_extension_symbols()) | set(L.declared_baseline_symbols())
-              | set(L.declared_product_symbols()) | set(L.declared_gap_symbols()) | set(L.declared_masked_symbols())
-              | set(L.declared_score_symbols()) | set(L.declared_lpips_symbols()))
-    assert not set(names) & others
-    assert all(hasattr(L.lib(), n) for n in names)
-    assert L.call("sifsr_abi_version") == 3
-
-
+# ---- 2. the pins of include/sifsr_conserve.h (the gate itself is tests/test_capi_gate.py) ---------------------------------------
 def test_the_writing_entry_point_has_contract_cases(L):
     from tests import test_conserve_gpu as T
-    writers = {n: p for n, p in _declarations().items() if p}
+    names, writers = L.declared("conserve"), L.writers("conserve")
+    assert names == ["sifsrk_conserve", "sifsrk_workspace_bytes"]
     assert writers == {"sifsrk_conserve": ["out", "stats", "workspace"]}
-    assert _declarations()["sifsrk_workspace_bytes"] == []
     assert sorted(T.CONTRACT) == sorted(writers)
     assert all(len(cases) >= 3 for cases in T.CONTRACT.values())
     # with and without a mask, in place and not, the pure check
@@ -258,5 +214,5 @@ def test_public_interface():
         conserve.consistency(z, torch.zeros((3, 3)))
     with pytest.raises(sifsr.SifsrError):
         conserve.conserve(z, torch.zeros((3, 3)))
-    assert os.path.samefile(sifsr._lib.CONSERVE_HEADER, os.path.join(ROOT, "include", "sifsr_conserve.h"))
+    assert os.path.samefile(sifsr._lib.header_path("conserve"), os.path.join(ROOT, "include", "sifsr_conserve.h"))
     assert sifsr.conserve is conserve and conserve.MAX_ITER == 64

@@ -21,9 +21,9 @@ import pytest
 import torch
 
 from tests import degrade_reference as R
-from tests.memcheck import Arena, Plain, bit_equal, same_under_all_poisons
+from tests.contract import L, S, bits, run_contract, sifsr  # noqa: F401  (L and sifsr are the fixtures)
+from tests.memcheck import bit_equal
 from tests.test_degrade_host import HOST_BAR
-from tests.test_memory_contract_gpu import K, S
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-4
@@ -36,29 +36,12 @@ BY = int(re.search(r"constexpr int BY = (\d+);", _SRC).group(1))
 
 
 @pytest.fixture(scope="module")
-def sifsr():
-    import sifsr as pkg
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return pkg
-
-
-@pytest.fixture(scope="module")
-def L(sifsr):
-    return sifsr._lib
-
-
-@pytest.fixture(scope="module")
 def gold():
     return np.load(GOLDEN)
 
 
 def dev(a):
     return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def bits(a):
-    a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
 def run(sifsr, x, factor, mtf=0.1, hkw=None, crop=False, valid=None, fill_value=float("nan")):
@@ -243,26 +226,13 @@ def degrade_case(i):
 CONTRACT = {"sifsrs_degrade": [degrade_case(i) for i in range(len(CONTRACT_SHAPES))]}
 
 
-def _execute(L, A, idx):
-    k = K(A, L, seed=431 + idx)
-    call, outs = CONTRACT["sifsrs_degrade"][idx](k)
-    torch.cuda.synchronize()
-    call()
-    torch.cuda.synchronize()
-    A.check()                                           # no guard byte and no const input changed
-    return {n: v.clone() for n, v in outs.items()}
-
-
 @pytest.mark.parametrize("idx", range(len(CONTRACT_SHAPES)))
 def test_memory_contract(L, idx):
     """out and out_valid written in full and nowhere else -- bit-identical and NaN-free under every poison of the outputs and of the
     workspace (no workspace byte is read before it is written; the NaNs of the invalid input pixels reach no output) --, x and valid
     untouched, nothing outside the buffers and the stated workspace bytes written, the same bits on ordinary allocations, and the
     result is the restatement's."""
-    first = same_under_all_poisons(lambda p: _execute(L, Arena("cuda", poison=p, capacity=64 << 20), idx))
-    plain = _execute(L, Plain("cuda"), idx)
-    for n, v in first.items():
-        assert bit_equal(v, plain[n]), f"{n}: the arena run and the ordinary-allocation run differ"
+    first = run_contract(L, CONTRACT["sifsrs_degrade"][idx], seed=431 + idx, capacity=64 << 20)
     B, h, w, factor, hkw, crop, with_valid, with_ov = CONTRACT_SHAPES[idx]
     x, valid = contract_inputs(idx)
     got = first["out"].cpu().numpy()

@@ -5,16 +5,14 @@
     regenerates from their seeds, and its own properties: both clamps are exercised, the fp32 coordinate rule matters within the
     limits, validity by brute force over stencils, a constant raster stays that constant,
   * output sizes: sifsr.degrade.output_shape / sifsrs_out_shape against the reference's own sizes on the whole recorded sweep,
-  * the gate of include/sifsr_degrade.h, restated from tests/test_conserve_host.py for the `sifsrs_` entry points: the exported
-    symbols are exactly the declared ones, none falls under the other headers, the writing entry point has memory-contract cases in
-    tests/test_degrade_gpu.py, the limits and error codes through the host-only paths,
+  * the pins of include/sifsr_degrade.h for the `sifsrs_` entry points (the gate itself is tests/test_capi_gate.py): the declared
+    names, the writing entry point has memory-contract cases in tests/test_degrade_gpu.py, the limits and error codes through the
+    host-only paths,
   * the public names and the drop-in names exist."""
 import ctypes
 import inspect
 import math
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -22,6 +20,7 @@ import pytest
 import torch
 
 from tests import degrade_reference as R
+from tests.capi_host import L  # noqa: F401  (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "golden_degrade_v1.npz")
@@ -29,16 +28,6 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "golden_degrade_v1.npz")
 # coarse_97x131: a 529-term fp32 sum of unknown order near 300 K); a bar above 1e-3 K would mean the restatement is wrong
 MEASURED_MAX = 3.080e-4
 HOST_BAR = 6.2e-4
-
-
-@pytest.fixture(scope="module")
-def L():
-    import sifsr  # noqa: F401
-    from sifsr import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib
 
 
 @pytest.fixture(scope="module")
@@ -171,46 +160,12 @@ def test_a_constant_raster_stays_that_constant():
             assert (np.abs(out[~ov] - 301.25) > 1e-6).all() and out[0, 0] < 200   # the ring met zeros (the cubic's lobes can overshoot)
 
 
-# ---- 2. the gate, restated for include/sifsr_degrade.h -----------------------------------------------------------------------------
-def _declarations():
-    """{name: [non-const pointer argument names]} of every SIFSR_API declaration of the header; the `stream` handle is not memory."""
-    text = open(os.path.join(ROOT, "include", "sifsr_degrade.h")).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    out = {}
-    for m in re.finditer(r"SIFSR_API\s+([\w\s]+?)\s+(\w+)\s*\(([^)]*)\)\s*;", text):
-        ptrs = []
-        for a in m.group(3).split(","):
-            a = " ".join(a.split())
-            mm = re.match(r"(.+?)\s*(\w+)$", a)
-            if mm and "*" in mm.group(1) and "const" not in mm.group(1) and mm.group(2) != "stream":
-                ptrs.append(mm.group(2))
-        out[m.group(2)] = ptrs
-    return out
-
-
-def test_exported_degrade_symbols_are_the_declared_ones(L):
-    names = L.declared_degrade_symbols()
-    assert set(names) == set(_declarations())
-    assert names == ["sifsrs_degrade", "sifsrs_out_shape", "sifsrs_workspace_bytes"]
-    assert all(n.startswith("sifsrs_") and "sifsr_" not in n for n in names)
-    handle = ctypes.CDLL(L.LIB_PATH)
-    assert not [n for n in names if not hasattr(handle, n)]
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("sifsrs_")}
-    assert exported == set(names), exported ^ set(names)
-    others = (set(L.declared_symbols()) | set(L.declared_extension_symbols()) | set(L.declared_baseline_symbols())
-              | set(L.declared_product_symbols()) | set(L.declared_gap_symbols()) | set(L.declared_masked_symbols())
-              | set(L.declared_score_symbols()) | set(L.declared_lpips_symbols()) | set(L.declared_conserve_symbols())
-              | set(L.declared_dms_symbols()) | set(L.declared_spectra_symbols()))
-    assert not set(names) & others
-    assert all(hasattr(L.lib(), n) for n in names)
-    assert L.call("sifsr_abi_version") == 3
-
-
+# ---- 2. the pins of include/sifsr_degrade.h (the gate itself is tests/test_capi_gate.py) ----------------------------------------
 def test_the_writing_entry_point_has_contract_cases(L):
     from tests import test_degrade_gpu as T
-    decl = _declarations()
-    assert decl["sifsrs_out_shape"] == ["oh", "ow"] and decl["sifsrs_workspace_bytes"] == []       # host only: two ints on the host
+    names, decl = L.declared("degrade"), L.writers("degrade")
+    assert names == ["sifsrs_degrade", "sifsrs_out_shape", "sifsrs_workspace_bytes"]
+    assert decl["sifsrs_out_shape"] == ["oh", "ow"] and "sifsrs_workspace_bytes" not in decl       # host only: two ints on the host
     writers = {n: p for n, p in decl.items() if p and n != "sifsrs_out_shape"}
     assert writers == {"sifsrs_degrade": ["out", "out_valid", "workspace"]}
     assert sorted(T.CONTRACT) == sorted(writers)
@@ -296,7 +251,7 @@ def test_public_interface():
     # the /4 operator keeps its refusals
     with pytest.raises(NotImplementedError):
         sifsr.sif_ops._taps_c(0.1, 2, None)
-    assert os.path.samefile(sifsr._lib.DEGRADE_HEADER, os.path.join(ROOT, "include", "sifsr_degrade.h"))
+    assert os.path.samefile(sifsr._lib.header_path("degrade"), os.path.join(ROOT, "include", "sifsr_degrade.h"))
 
 
 def test_dropin_names_resolve():

@@ -6,7 +6,7 @@
   * end to end against tests/golden/golden_dms_v1.npz (the reference's tree class inside BaggingRegressor),
   * batch rows bit-equal to single-image calls, the same seed the same bits, an image with fewer than 10 good cells all NaN,
   * the memory contract of every writing entry point in the guarded, poisoned arena of tests/memcheck.py (CONTRACT below is the
-    table tests/test_dms_host.py checks against the header), the argument errors and the drop-in name.
+    table tests/test_capi_gate.py checks against the header), the argument errors and the drop-in name.
 
 Bounds.  Tree structure (thresholds, leaf counts): exact.  Rasters: 1e-4 K, the bar tests/test_baselines_gpu.py applies to TsHARP
 against its restatement (float64 arithmetic, one float32 rounding, spacing 3.05e-5 K at 256..512 K).  float64 stage outputs:
@@ -22,8 +22,8 @@ import pytest
 import torch
 
 from tests import dms_reference as R
-from tests.memcheck import Arena, Plain, bit_equal, same_under_all_poisons
-from tests.test_memory_contract_gpu import K, S
+from tests.contract import L, S, run_contract, sifsr  # noqa: F401  (L and sifsr are the fixtures)
+from tests.memcheck import bit_equal
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,21 +38,9 @@ SHAPES = {(4, 4): (1, 1), (5, 7): (1, 1), (16, 16): (1, 1), (17, 23): (1, 1)}
 
 
 @pytest.fixture(scope="module")
-def sifsr():
-    import sifsr as pkg
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return pkg
-
-
-@pytest.fixture(scope="module")
 def BL(sifsr):
     from sifsr import baselines
     return baselines
-
-
-@pytest.fixture(scope="module")
-def L(sifsr):
-    return sifsr._lib
 
 
 @pytest.fixture(scope="module")
@@ -376,24 +364,11 @@ CONTRACT = {
 CASES = [(name, i) for name, cases in CONTRACT.items() for i in range(len(cases))]
 
 
-def _execute(L, A, name, idx):
-    k = K(A, L, seed=sum(map(ord, name)) * 131 + idx)
-    call, outs = CONTRACT[name][idx](k)
-    torch.cuda.synchronize()
-    call()
-    torch.cuda.synchronize()
-    A.check()                                           # no guard byte and no const input changed
-    return {n: v.clone() for n, v in outs.items()}
-
-
 @pytest.mark.parametrize("name,idx", CASES, ids=[f"{n[7:]}-{i}" for n, i in CASES])
 def test_memory_contract(L, name, idx):
     """every output fully written -- NaN-free under the NaN poison, bit-identical under every poison --, inputs untouched, nothing
     outside the buffers written (the fit's scratch included), and the same bits on ordinary allocations."""
-    first = same_under_all_poisons(lambda p: _execute(L, Arena("cuda", poison=p, capacity=64 << 20), name, idx))
-    plain = _execute(L, Plain("cuda"), name, idx)
-    for n, v in first.items():
-        assert bit_equal(v, plain[n]), f"{n}: the arena run and the ordinary-allocation run differ"
+    run_contract(L, CONTRACT[name][idx], seed=sum(map(ord, name)) * 131 + idx, capacity=64 << 20)
 
 
 # ---- 5. errors ---------------------------------------------------------------------------------------------------------------

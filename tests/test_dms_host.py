@@ -7,19 +7,17 @@
     distinct leaf values (a condition on the inputs, not a tolerance: a near-tie may flip under another summation order),
   * where scikit-learn is installed, the restatement's trees are those of a live DecisionTreeRegressor on seeded data with
     duplicate features and zero weights,
-  * the gate of include/sifsr_dms.h, restated from tests/test_baselines_host.py for the `sifsrd_` entry points,
+  * the pins of include/sifsr_dms.h for the `sifsrd_` entry points (the gate itself is tests/test_capi_gate.py),
   * the public interface, its refusals, and the drop-in name."""
 import ast
-import ctypes
 import inspect
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import dms_reference as R
+from tests.capi_host import L  # noqa: F401  (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = [0, 1, 2, 3]
@@ -29,16 +27,6 @@ PROXY_GAP, HEAP_GAP = 1e-10, 1e-6
 @pytest.fixture(scope="module")
 def golden():
     return np.load(os.path.join(ROOT, "tests", "golden", "golden_dms_v1.npz"))
-
-
-@pytest.fixture(scope="module")
-def L():
-    import sifsr  # noqa: F401
-    from sifsr import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib
 
 
 _FITS = {}
@@ -161,48 +149,14 @@ def test_few_good_cells_give_no_model():
     assert info["ts"]["n_train"] == 0 and np.isnan(out).all() and out.shape == (16, 16)
 
 
-# ---- the gate, restated for include/sifsr_dms.h -----------------------------------------------------------------------------
-def _declarations():
-    text = open(os.path.join(ROOT, "include", "sifsr_dms.h")).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    out = {}
-    for m in re.finditer(r"SIFSR_API\s+([\w\s]+?)\s+(\w+)\s*\(([^)]*)\)\s*;", text):
-        ptrs = []
-        for a in m.group(3).split(","):
-            a = " ".join(a.split())
-            mm = re.match(r"(.+?)\s*(\w+)$", a)
-            if mm and "*" in mm.group(1) and "const" not in mm.group(1) and mm.group(2) != "stream":
-                ptrs.append(mm.group(2))
-        out[m.group(2)] = ptrs
-    return out
-
-
-def test_exported_dms_symbols_are_the_declared_ones(L):
-    names = L.declared_dms_symbols()
-    assert set(names) == set(_declarations()) and len(names) == 7
-    assert all(n.startswith("sifsrd_") and "sifsr_" not in n for n in names)
-    handle = ctypes.CDLL(L.LIB_PATH)
-    assert not [n for n in names if not hasattr(handle, n)]
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("sifsrd_")}
-    assert exported == set(names), exported ^ set(names)
-    others = set(L.declared_symbols()) | set(L.declared_extension_symbols()) | set(L.declared_baseline_symbols()) \
-        | set(L.declared_conserve_symbols())
-    assert not set(names) & others
-    assert all(hasattr(L.lib(), n) for n in names)
-    assert L.call("sifsr_abi_version") == 3
-
-
+# ---- the pins of include/sifsr_dms.h (the gate itself is tests/test_capi_gate.py) --------------------------------------------
 def test_every_writing_dms_entry_point_has_a_contract_case(L):
     from tests import test_dms_gpu as T
-    writers = {n: p for n, p in _declarations().items() if p}
+    writers = L.writers("dms")
+    assert len(L.declared("dms")) == 7
     assert writers == {"sifsrd_aggregate": ["mean", "std"], "sifsrd_trainset": ["x", "cv", "good"], "sifsrd_weights": ["weight"],
                        "sifsrd_fit": ["scratch", "thresholds", "nleaf", "leaves"], "sifsrd_predict": ["sr"],
                        "sifsrd_correct": ["out"]}
-    missing = sorted(set(writers) - set(T.CONTRACT))
-    assert not missing, f"no memory-contract case for {missing}: add a row to CONTRACT in tests/test_dms_gpu.py"
-    stale = sorted(set(T.CONTRACT) - set(writers))
-    assert not stale, f"CONTRACT rows for entry points the header does not declare as writers: {stale}"
     assert all(len(cases) >= 3 for cases in T.CONTRACT.values())
 
 

@@ -10,7 +10,7 @@ Rasters (LST in [250, 350] K, seeded: gaps_reference.make_rasters), the smallest
     64x64     all valid            40x40   all invalid            33x33   one valid pixel at (32, 32): the fill is the top level
 
   * the memory contract of the four writing entry points in the guarded, poisoned arena of tests/memcheck.py (CONTRACT below is the
-    table tests/test_gaps_host.py checks against the header); `x` tiles and `active` entries past n_active keep their poison, the
+    table tests/test_capi_gate.py checks against the header); `x` tiles and `active` entries past n_active keep their poison, the
     fill workspace is poisoned scratch,
   * fill, select, compact prepare and masked blend for equality -- with the restatement, with sifsrx_tiles_prepare on the filled
     raster, with sifsrx_tiles_blend on the full tile set,
@@ -26,35 +26,14 @@ import torch
 
 from oracle import sif_oracle as O
 from tests import gaps_reference as R
-from tests.memcheck import Arena, Partial, Plain, bit_equal, same_under_all_poisons
-from tests.test_memory_contract_gpu import K, S
+from tests.contract import L, S, bits, dev, run_contract, sifsr  # noqa: F401  (L and sifsr are the fixtures)
+from tests.memcheck import Partial, bit_equal
 from tests.test_mosaic_gpu import STATS, _granule, _model, origins
 
 pytestmark = pytest.mark.gpu
 I32, U8 = torch.int32, torch.uint8
 SHAPE_ERR, ARG_ERR, WORKSPACE_ERR = 1001, 1002, 1003
 RASTERS = R.make_rasters()
-
-
-@pytest.fixture(scope="module")
-def sifsr():
-    import sifsr as pkg
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return pkg
-
-
-@pytest.fixture(scope="module")
-def L(sifsr):
-    return sifsr._lib
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a)).cuda()                    # (a copy: the rasters are read-only)
-
-
-def bits(a):
-    a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
 def ntiles(h, w, win, overlap, cover):
@@ -153,37 +132,12 @@ CONTRACT = {"sifsrg_fill": [fill_case(i, m) for i in R4 for m in (False, True)],
 CASES = [(name, i) for name, cases in CONTRACT.items() for i in range(len(cases))]
 
 
-def _execute(L, A, name, idx):
-    k = K(A, L, seed=sum(map(ord, name)) * 131 + idx)
-    call, outs = CONTRACT[name][idx](k)
-    torch.cuda.synchronize()
-    call()
-    torch.cuda.synchronize()
-    A.check()                                           # no guard byte and no const input changed
-    res = {}
-    for n, v in outs.items():
-        if callable(v):
-            p = v()
-            res[n] = Partial(p.tensor.clone(), p.written, p.initial)
-        else:
-            res[n] = v.clone()
-    return res
-
-
 @pytest.mark.parametrize("name,idx", CASES, ids=[f"{n[7:]}-{i}" for n, i in CASES])
 def test_memory_contract(L, name, idx):
     """every output written where the header says and nowhere else -- NaN-free under the NaN poison, bit-identical under every
     poison (the poisoned fill workspace included), `x` tiles and `active` entries past n_active still holding their poison --,
     inputs untouched, nothing outside the buffers written, and the same bits on ordinary allocations."""
-    first = same_under_all_poisons(lambda p: _execute(L, Arena("cuda", poison=p, capacity=64 << 20), name, idx))
-    plain = _execute(L, Plain("cuda"), name, idx)
-    for n, v in first.items():
-        other = plain[n]
-        if isinstance(other, Partial):
-            w = other.written.to(other.tensor.device).expand_as(other.tensor)
-            other = other.tensor.clone()
-            other[~w] = 0
-        assert bit_equal(v, other), f"{n}: the arena run and the ordinary-allocation run differ"
+    run_contract(L, CONTRACT[name][idx], seed=sum(map(ord, name)) * 131 + idx, capacity=64 << 20)
 
 
 def test_workspace_too_small(L):

@@ -4,33 +4,17 @@
     for bit on every raster of the GPU tests, with and without a mask, and the planted gaps reach the code paths they are meant to,
   * select_ref over the layout sweep of tests/test_mosaic_host.py on random masks: `active` sorted, `slot` and `active` inverse to
     each other, every tile that covers a valid pixel active,
-  * the gate of include/sifsr_gaps.h, restated from tests/test_mosaic_host.py for the `sifsrg_` entry points: the exported symbols
-    are exactly the declared ones, none falls under the other four headers, every entry point that can write through a pointer has
-    a memory-contract case in tests/test_gaps_gpu.py."""
-import ctypes
-import os
-import re
-import subprocess
-
+  * the pins of include/sifsr_gaps.h for the `sifsrg_` entry points (the gate itself is tests/test_capi_gate.py): the declared
+    names, every entry point that can write through a pointer has a memory-contract case in tests/test_gaps_gpu.py."""
 import numpy as np
 import pytest
 
 from tests import gaps_reference as R
+from tests.capi_host import L  # noqa: F401  (the fixture)
 from tests.test_mosaic_gpu import origins
 from tests.test_mosaic_host import _sweep
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RASTERS = R.make_rasters()
-
-
-@pytest.fixture(scope="module")
-def L():
-    import sifsr  # noqa: F401
-    from sifsr import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib
 
 
 def bits(a):
@@ -124,49 +108,14 @@ def test_masked_blend_restatement():
         assert (up & ~m).any() == (cover == 0)
 
 
-# ---- 3. the gate, restated for include/sifsr_gaps.h ----------------------------------------------------------------------------
-def _declarations():
-    """{name: [non-const pointer argument names]} of every SIFSR_API declaration of the header; the `stream` handle is not memory."""
-    text = open(os.path.join(ROOT, "include", "sifsr_gaps.h")).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    out = {}
-    for m in re.finditer(r"SIFSR_API\s+([\w\s]+?)\s+(\w+)\s*\(([^)]*)\)\s*;", text):
-        ptrs = []
-        for a in m.group(3).split(","):
-            a = " ".join(a.split())
-            mm = re.match(r"(.+?)\s*(\w+)$", a)
-            if mm and "*" in mm.group(1) and "const" not in mm.group(1) and mm.group(2) != "stream":
-                ptrs.append(mm.group(2))
-        out[m.group(2)] = ptrs
-    return out
-
-
-def test_exported_gap_symbols_are_the_declared_ones(L):
-    names = L.declared_gap_symbols()
-    assert set(names) == set(_declarations()) and len(names) == 5
-    assert all(n.startswith("sifsrg_") and "sifsr_" not in n for n in names)
-    handle = ctypes.CDLL(L.LIB_PATH)
-    assert not [n for n in names if not hasattr(handle, n)]
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("sifsrg_")}
-    assert exported == set(names), exported ^ set(names)
-    others = (set(L.declared_symbols()) | set(L.declared_extension_symbols()) | set(L.declared_baseline_symbols())
-              | set(L.declared_product_symbols()))
-    assert not set(names) & others
-    assert all(hasattr(L.lib(), n) for n in names)
-    assert L.call("sifsr_abi_version") == 3
-
-
+# ---- 3. the pins of include/sifsr_gaps.h (the gate itself is tests/test_capi_gate.py) -------------------------------------------
 def test_every_writing_gap_entry_point_has_a_contract_case(L):
     from tests import test_gaps_gpu as T
-    writers = {n: p for n, p in _declarations().items() if p}
+    writers = L.writers("gaps")
+    assert len(L.declared("gaps")) == 5
     assert writers == {"sifsrg_fill": ["filled", "valid", "workspace"], "sifsrg_tiles_select": ["slot", "active", "n_active"],
                        "sifsrg_tiles_prepare": ["x"], "sifsrg_tiles_blend": ["out"]}
-    assert _declarations()["sifsrg_fill_workspace_bytes"] == []                # host only, no pointers: not a writer
-    missing = sorted(set(writers) - set(T.CONTRACT))
-    assert not missing, f"no memory-contract case for {missing}: add a row to CONTRACT in tests/test_gaps_gpu.py"
-    stale = sorted(set(T.CONTRACT) - set(writers))
-    assert not stale, f"CONTRACT rows for entry points the header does not declare as writers: {stale}"
+    assert "sifsrg_fill_workspace_bytes" in L.declared("gaps")                 # host only, no pointers: not a writer
     assert all(len(cases) >= 4 for cases in T.CONTRACT.values())
 
 

@@ -9,7 +9,7 @@
     three-channel call on hand-normalised repeated channels (which holds the on-device min / max to the restatement's), a
     constant pair -> NaN, one NaN pixel -> that row NaN and the others untouched;
   * the memory contract of the three writing entry points in the guarded, poisoned arena of tests/memcheck.py (CONTRACT below is
-    the list tests/test_lpips_host.py gates), error codes with `out6` untouched, one linear hipGraph capture;
+    the list tests/test_capi_gate.py gates), error codes with `out6` untouched, one linear hipGraph capture;
   * the Python interface: both key forms, the reductions, lists of mixed sizes, the nine-column table."""
 import ctypes
 
@@ -18,28 +18,13 @@ import pytest
 import torch
 
 from tests import lpips_reference as R
-from tests.memcheck import Arena, Plain, bit_equal, same_under_all_poisons
+from tests.contract import L, S, run_contract, sifsr  # noqa: F401  (L and sifsr are the fixtures)
+from tests.memcheck import bit_equal
 
 pytestmark = pytest.mark.gpu
 F64, U8 = torch.float64, torch.uint8
 TOL = 1e-4
 ZERO3, ONE3 = [0.0, 0.0, 0.0], [1.0, 1.0, 1.0]
-
-
-@pytest.fixture(scope="module")
-def sifsr():
-    import sifsr as pkg
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return pkg
-
-
-@pytest.fixture(scope="module")
-def L(sifsr):
-    return sifsr._lib
-
-
-def S():
-    return torch.cuda.current_stream().cuda_stream
 
 
 @pytest.fixture(scope="module")
@@ -146,13 +131,6 @@ def test_one_non_finite_pixel(L, packed, bad):
 
 
 # ---- 3. memory contract ----------------------------------------------------------------------------------------------------------
-class K:
-    """one run's view of the allocator (tests/test_memory_contract_gpu.py's K, with inputs in [0, 1])"""
-
-    def __init__(self, A, L, seed):
-        self.A, self.L, self.seed = A, L, seed
-
-
 _PACKED_CPU = {}
 
 
@@ -204,25 +182,12 @@ CONTRACT = {"sifsrl_pack": [pack_case(s) for s in (1.0, 0.5, -2.0)],
 CASES = [(name, i) for name, cases in CONTRACT.items() for i in range(len(cases))]
 
 
-def _execute(L, A, name, idx):
-    k = K(A, L, seed=sum(map(ord, name)) * 131 + idx)
-    call, outs = CONTRACT[name][idx](k)
-    torch.cuda.synchronize()
-    call()
-    torch.cuda.synchronize()
-    A.check()                                           # no guard byte and no const input (`packed` included) changed
-    return {n: v.clone() for n, v in outs.items()}
-
-
 @pytest.mark.parametrize("name,idx", CASES, ids=[f"{n[7:]}-{i}" for n, i in CASES])
 def test_memory_contract(L, name, idx):
     """every output written in full and nowhere else -- NaN-free under the NaN poison, bit-identical under every poison (the
     poisoned workspace included: nothing is left over from an earlier call) --, const inputs untouched, and the same bits on
     ordinary allocations."""
-    first = same_under_all_poisons(lambda p: _execute(L, Arena("cuda", poison=p, capacity=160 << 20), name, idx))
-    plain = _execute(L, Plain("cuda"), name, idx)
-    for n, v in first.items():
-        assert bit_equal(v, plain[n]), f"{n}: the arena run and the ordinary-allocation run differ"
+    run_contract(L, CONTRACT[name][idx], seed=sum(map(ord, name)) * 131 + idx, capacity=160 << 20)
 
 
 def test_error_codes_leave_out6_untouched(L, packed):

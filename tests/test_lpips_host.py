@@ -1,37 +1,27 @@
 """CPU: on-device LPIPS -- what can be held without a GPU.
 
-  * the float64 restatement tests/lpips_reference.py against the golden file (whose maker ran the reference's own ContentLoss on the
+  * the float64 restatement tests/lpips_reference.py against the golden file (whose maker ran the reference's own ContentLoss on
+    the
     same weights), the checksum of the closed-form weights, an identical pair -> 0,
   * the planted cases: every non-identical case of the GPU value tests and of the golden file has all five layer terms >= 1e-7 in
     float64, so no layer can pass as 0 = 0,
-  * the gate of include/sifsr_lpips.h, restated from tests/test_scores_host.py for the `sifsrl_` entry points: the exported symbols
-    are exactly the declared ones, none falls under the other headers, every entry point that can write through a pointer has at
-    least three memory-contract cases in tests/test_lpips_gpu.py; sizes and error codes through the host-only paths,
+  * the pins of include/sifsr_lpips.h for the `sifsrl_` entry points (the gate itself is tests/test_capi_gate.py): the declared
+    names, every entry point that can write through a pointer has at least three memory-contract cases in tests/test_lpips_gpu.py;
+    sizes and error codes through the host-only paths,
   * the public interface and its errors, the drop-in without weights included."""
 import ctypes
 import importlib.util
 import inspect
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import lpips_reference as R
+from tests.capi_host import L  # noqa: F401  (the fixture)
 
 ROOT = R.ROOT
-
-
-@pytest.fixture(scope="module")
-def L():
-    import sifsr  # noqa: F401
-    from sifsr import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib
 
 
 # ---- 1. the restatement and the generator ----------------------------------------------------------------------------------------
@@ -80,46 +70,13 @@ def test_planted_cases_are_above_the_floor():
     assert R.FLOOR == 1e-7 and smallest >= R.FLOOR
 
 
-# ---- 2. the gate, restated for include/sifsr_lpips.h -----------------------------------------------------------------------------
-def _declarations():
-    """{name: [non-const pointer argument names]} of every SIFSR_API declaration of the header; the `stream` handle is not memory."""
-    text = open(os.path.join(ROOT, "include", "sifsr_lpips.h")).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    out = {}
-    for m in re.finditer(r"SIFSR_API\s+([\w\s]+?)\s+(\w+)\s*\(([^)]*)\)\s*;", text):
-        ptrs = []
-        for a in m.group(3).split(","):
-            a = " ".join(a.split())
-            mm = re.match(r"(.+?)\s*(\w+)$", a)
-            if mm and "*" in mm.group(1) and "const" not in mm.group(1) and mm.group(2) != "stream":
-                ptrs.append(mm.group(2))
-        out[m.group(2)] = ptrs
-    return out
-
-
-def test_exported_lpips_symbols_are_the_declared_ones(L):
-    names = L.declared_lpips_symbols()
-    assert set(names) == set(_declarations())
-    assert names == ["sifsrl_lpips", "sifsrl_lpips_pairs", "sifsrl_pack", "sifsrl_pack_floats", "sifsrl_workspace_bytes"]
-    assert all(n.startswith("sifsrl_") and "sifsr_" not in n for n in names)
-    handle = ctypes.CDLL(L.LIB_PATH)
-    assert not [n for n in names if not hasattr(handle, n)]
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("sifsrl_")}
-    assert exported == set(names), exported ^ set(names)
-    others = (set(L.declared_symbols()) | set(L.declared_extension_symbols()) | set(L.declared_baseline_symbols())
-              | set(L.declared_product_symbols()) | set(L.declared_gap_symbols()) | set(L.declared_masked_symbols())
-              | set(L.declared_score_symbols()))
-    assert not set(names) & others
-    assert all(hasattr(L.lib(), n) for n in names)
-    assert L.call("sifsr_abi_version") == 3
-
-
+# ---- 2. the pins of include/sifsr_lpips.h (the gate itself is tests/test_capi_gate.py) ------------------------------------------
 def test_every_writing_lpips_entry_point_has_contract_cases(L):
     from tests import test_lpips_gpu as T
-    writers = {n: p for n, p in _declarations().items() if p}
+    names, writers = L.declared("lpips"), L.writers("lpips")
+    assert names == ["sifsrl_lpips", "sifsrl_lpips_pairs", "sifsrl_pack", "sifsrl_pack_floats", "sifsrl_workspace_bytes"]
     assert writers == {"sifsrl_pack": ["packed"], "sifsrl_lpips": ["workspace", "out6"], "sifsrl_lpips_pairs": ["workspace", "out6"]}
-    assert all(_declarations()[n] == [] for n in ("sifsrl_pack_floats", "sifsrl_workspace_bytes"))
+    assert all(n not in writers for n in ("sifsrl_pack_floats", "sifsrl_workspace_bytes"))
     assert sorted(T.CONTRACT) == sorted(writers)
     assert all(len(cases) >= 3 for cases in T.CONTRACT.values())
 
@@ -174,7 +131,7 @@ def test_public_interface_and_errors(tmp_path, monkeypatch):
     assert metrics.METRIC_NAMES == metrics.METRIC_NAMES_WITH_LPIPS[:7] + metrics.METRIC_NAMES_WITH_LPIPS[8:] and len(metrics.METRIC_NAMES) == 8
     assert lpips.IMAGENET_MEAN == R.IMAGENET_MEAN and lpips.IMAGENET_STD == R.IMAGENET_STD
     assert lpips.N_VGG_PARAMS == 14714688 and lpips.N_LIN == 1472 and lpips.CONV_MODULES == R.CONV_MODULES
-    assert os.path.samefile(sifsr._lib.LPIPS_HEADER, os.path.join(ROOT, "include", "sifsr_lpips.h"))
+    assert os.path.samefile(sifsr._lib.header_path("lpips"), os.path.join(ROOT, "include", "sifsr_lpips.h"))
 
     # both key forms, piq's list, paths: the flat buffers are the generator's
     for prefix in ("features.", ""):

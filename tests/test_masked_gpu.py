@@ -2,7 +2,7 @@
 tests/masked_reference.py (held to the oracle by tests/test_masked_host.py) and against the unmasked entry points.
 
   * the memory contract of the two writing entry points in the guarded, poisoned arena of tests/memcheck.py (CONTRACT below is the
-    table tests/test_masked_host.py checks against the header); the loss workspace is poisoned scratch,
+    table tests/test_capi_gate.py checks against the header); the loss workspace is poisoned scratch,
   * fill: N = 4 patches (all valid, none valid, one valid pixel, a hole with scattered zeros, a NaN and an inf) at w = 8, 20, 64,
     bit-equal to the restatement and to sifsrg_fill per patch, moments exact (M2 to 1e-12), a row of a batch = its N = 1 call,
   * loss: B = 2 at (40, 24), (64, 64), (100, 36) -- partial 32 x 32 tiles, a last row of tiles with partial LR blocks --, both
@@ -17,8 +17,8 @@ import torch
 from oracle import sif_oracle as O
 from tests import masked_reference as R
 from tests.conftest import rel_err
-from tests.memcheck import Arena, Plain, bit_equal, same_under_all_poisons
-from tests.test_memory_contract_gpu import K, S
+from tests.contract import L, S, run_contract, sifsr  # noqa: F401  (L and sifsr are the fixtures)
+from tests.memcheck import bit_equal
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4                                   # tests/test_ops_gpu.py: the bar of the unmasked fused loss
@@ -26,18 +26,6 @@ U8, I64, F64 = torch.uint8, torch.int64, torch.float64
 WORKSPACE_ERR = 1003
 MEAN, STD = R.MEAN, R.STD
 KIND_ID = {"sr2": 2, "sr1": 1}
-
-
-@pytest.fixture(scope="module")
-def sifsr():
-    import sifsr as pkg
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return pkg
-
-
-@pytest.fixture(scope="module")
-def L(sifsr):
-    return sifsr._lib
 
 
 def dev(a):
@@ -90,24 +78,11 @@ CONTRACT = {"sifsrm_patches_fill": [fill_case(w) for w in (4, 8, 20, 64)],
 CASES = [(name, i) for name, cases in CONTRACT.items() for i in range(len(cases))]
 
 
-def _execute(L, A, name, idx):
-    k = K(A, L, seed=sum(map(ord, name)) * 131 + idx)
-    call, outs = CONTRACT[name][idx](k)
-    torch.cuda.synchronize()
-    call()
-    torch.cuda.synchronize()
-    A.check()                                           # no guard byte and no const input changed
-    return {n: v.clone() for n, v in outs.items()}
-
-
 @pytest.mark.parametrize("name,idx", CASES, ids=[f"{n[7:]}-{i}" for n, i in CASES])
 def test_memory_contract(L, name, idx):
     """every output written in full and nowhere else -- NaN-free under the NaN poison, bit-identical under every poison (the
     poisoned loss workspace included) --, const inputs untouched, and the same bits on ordinary allocations."""
-    first = same_under_all_poisons(lambda p: _execute(L, Arena("cuda", poison=p, capacity=64 << 20), name, idx))
-    plain = _execute(L, Plain("cuda"), name, idx)
-    for n, v in first.items():
-        assert bit_equal(v, plain[n]), f"{n}: the arena run and the ordinary-allocation run differ"
+    run_contract(L, CONTRACT[name][idx], seed=sum(map(ord, name)) * 131 + idx, capacity=64 << 20)
 
 
 def test_workspace_too_small(sifsr, L):

@@ -5,15 +5,11 @@
     pixels changes nothing, n = 0 gives zeros,
   * the inputs of the GPU loss tests reach both Huber branches: a condition on the inputs, asserted here,
   * the per-patch fill restatement: the planted patches are what they are meant to be, the moments are NumPy's,
-  * the gate of include/sifsr_masked.h, restated from tests/test_gaps_host.py for the `sifsrm_` entry points: the exported symbols
-    are exactly the declared ones, none contains `sifsr_` or falls under the other headers, every entry point that can write
-    through a pointer has a memory-contract case in tests/test_masked_gpu.py,
+  * the pins of include/sifsr_masked.h for the `sifsrm_` entry points (the gate itself is tests/test_capi_gate.py): the declared
+    names, every entry point that can write through a pointer has a memory-contract case in tests/test_masked_gpu.py,
   * the public names exist with the defaults that leave every existing call as it was."""
 import ctypes
 import inspect
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,20 +18,10 @@ import torch
 from oracle import sif_oracle as O
 from tests import gaps_reference as G
 from tests import masked_reference as R
+from tests.capi_host import L  # noqa: F401  (the fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = [(hw, k, m) for hw in R.SHAPES for k in R.KINDS for m in R.MASKS]
 IDS = [f"{hw[0]}x{hw[1]}-{k[0]}-a{k[1]}-{m}" for hw, k, m in CASES]
-
-
-@pytest.fixture(scope="module")
-def L():
-    import sifsr  # noqa: F401
-    from sifsr import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib
 
 
 # ---- 1. the masked loss against the oracle -------------------------------------------------------------------------------------
@@ -122,44 +108,13 @@ def test_ten_percent_holes():
     assert p.astype(np.float64).mean() <= 0.9 * 310
 
 
-# ---- 3. the gate, restated for include/sifsr_masked.h --------------------------------------------------------------------------
-def _declarations():
-    """{name: [non-const pointer argument names]} of every SIFSR_API declaration of the header; the `stream` handle is not memory."""
-    text = open(os.path.join(ROOT, "include", "sifsr_masked.h")).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    out = {}
-    for m in re.finditer(r"SIFSR_API\s+([\w\s]+?)\s+(\w+)\s*\(([^)]*)\)\s*;", text):
-        ptrs = []
-        for a in m.group(3).split(","):
-            a = " ".join(a.split())
-            mm = re.match(r"(.+?)\s*(\w+)$", a)
-            if mm and "*" in mm.group(1) and "const" not in mm.group(1) and mm.group(2) != "stream":
-                ptrs.append(mm.group(2))
-        out[m.group(2)] = ptrs
-    return out
-
-
-def test_exported_masked_symbols_are_the_declared_ones(L):
-    names = L.declared_masked_symbols()
-    assert set(names) == set(_declarations()) and names == ["sifsrm_patches_fill", "sifsrm_sif_loss", "sifsrm_sif_loss_workspace_bytes"]
-    assert all(n.startswith("sifsrm_") and "sifsr_" not in n for n in names)
-    handle = ctypes.CDLL(L.LIB_PATH)
-    assert not [n for n in names if not hasattr(handle, n)]
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("sifsrm_")}
-    assert exported == set(names), exported ^ set(names)
-    others = (set(L.declared_symbols()) | set(L.declared_extension_symbols()) | set(L.declared_baseline_symbols())
-              | set(L.declared_product_symbols()) | set(L.declared_gap_symbols()))
-    assert not set(names) & others
-    assert all(hasattr(L.lib(), n) for n in names)
-    assert L.call("sifsr_abi_version") == 3
-
-
+# ---- 3. the pins of include/sifsr_masked.h (the gate itself is tests/test_capi_gate.py) -----------------------------------------
 def test_every_writing_masked_entry_point_has_a_contract_case(L):
     from tests import test_masked_gpu as T
-    writers = {n: p for n, p in _declarations().items() if p}
+    names, writers = L.declared("masked"), L.writers("masked")
+    assert names == ["sifsrm_patches_fill", "sifsrm_sif_loss", "sifsrm_sif_loss_workspace_bytes"]
     assert writers == {"sifsrm_patches_fill": ["filled", "valid", "moments"], "sifsrm_sif_loss": ["workspace", "losses3", "dsr"]}
-    assert _declarations()["sifsrm_sif_loss_workspace_bytes"] == []           # host only, no pointers: not a writer
+    assert "sifsrm_sif_loss_workspace_bytes" not in writers                   # host only, no pointers: not a writer
     assert sorted(T.CONTRACT) == sorted(writers)
     assert all(len(cases) >= 3 for cases in T.CONTRACT.values())
 

@@ -9,62 +9,18 @@ case runs under the three poisons:
   * the same call on ordinary allocations gives the same bits (carving cannot change which path runs).
 
 Nothing takes a tolerance.  The operands are random but well-scaled: the contract does not depend on them being a consistent
-forward state.  CONTRACT is also the coverage table tests/test_memory_contract_host.py checks against the header."""
+forward state.  CONTRACT is also the coverage table tests/test_capi_gate.py checks against the header."""
 import numpy as np
 import pytest
 import torch
 
-from tests.memcheck import Arena, Partial, Plain, bit_equal, same_under_all_poisons
+from tests.contract import L, S, run_contract, sifsr  # noqa: F401  (L and sifsr are the fixtures)
+from tests.memcheck import Partial, bit_equal
 
 pytestmark = pytest.mark.gpu
 
 F32, BF16, F64 = torch.float32, torch.bfloat16, torch.float64
 ENGINE_ENTRY_POINTS = ("sifsr_model_forward", "sifsr_model_backward", "sifsr_model_forward_ex", "sifsr_model_backward_ex")
-
-
-@pytest.fixture(scope="module")
-def L():
-    import sifsr  # noqa: F401
-    from sifsr import _lib
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return _lib
-
-
-def S():
-    return torch.cuda.current_stream().cuda_stream
-
-
-class K:
-    """One run's view of the allocator: seeded operands in, poisoned outputs out."""
-
-    def __init__(self, A, L, seed):
-        self.A, self.L, self.rs = A, L, np.random.RandomState(seed)
-
-    def i(self, name, *shape, scale=1.0, shift=0.0, dtype=F32):
-        t = torch.from_numpy((self.rs.standard_normal(shape) * scale + shift).astype(np.float32)).to(dtype)
-        return self.A.input(t, name)
-
-    def pos(self, name, n):
-        return self.A.input(torch.from_numpy(self.rs.uniform(0.5, 1.5, n).astype(np.float32)), name)
-
-    def t(self, name, tensor):
-        return self.A.input(tensor, name)
-
-    def o(self, name, *shape, dtype=F32):
-        return self.A.output(shape, dtype, name)
-
-    def s(self, name, nfloats):
-        assert nfloats > 0, name
-        return self.A.scratch(int(nfloats) * 4, name)
-
-    def border(self, name, B, H, W, C, dtype=F32):
-        """the border scratch: only the image-border pixels are written"""
-        b = self.A.output((B, H, W, C), dtype, name)
-        m = torch.zeros(1, H, W, 1, dtype=torch.bool)
-        m[:, 0] = m[:, -1] = True
-        m[:, :, 0] = m[:, :, -1] = True
-        init = b.clone()
-        return b, (lambda: Partial(b, m, init))
 
 
 _PACKS = {}
@@ -776,38 +732,13 @@ CONTRACT = {
 CASES = [(name, i) for name, cases in CONTRACT.items() if cases is not ENGINE for i in range(len(cases))]
 
 
-def _execute(L, A, name, idx):
-    k = K(A, L, seed=sum(map(ord, name)) * 131 + idx)
-    call, outs = CONTRACT[name][idx](k)
-    torch.cuda.synchronize()
-    call()
-    torch.cuda.synchronize()
-    A.check()
-    res = {}
-    for n, v in outs.items():
-        if callable(v):
-            p = v()
-            res[n] = Partial(p.tensor.clone(), p.written, p.initial)
-        else:
-            res[n] = v.clone()
-    return res
-
-
 @pytest.mark.parametrize("name,idx", CASES, ids=[f"{n[6:]}-{i}" for n, i in CASES])
 def test_memory_contract(L, name, idx):
-    first = same_under_all_poisons(lambda p: _execute(L, Arena("cuda", poison=p), name, idx))
-    plain = _execute(L, Plain("cuda"), name, idx)
-    for n, v in first.items():
-        ref = plain[n]
-        if isinstance(ref, Partial):
-            w = ref.written.to(ref.tensor.device).expand_as(ref.tensor)
-            assert bit_equal(v[w], ref.tensor[w]), f"{n}: the arena run and the ordinary-allocation run differ"
-        else:
-            assert bit_equal(v, ref), f"{n}: the arena run and the ordinary-allocation run differ"
+    run_contract(L, CONTRACT[name][idx], seed=sum(map(ord, name)) * 131 + idx)
 
 
 def test_table_is_complete():
-    """every row has cases and every case index is reachable (the header-side gate is tests/test_memory_contract_host.py)"""
+    """every row has cases and every case index is reachable (the header-side gate is tests/test_capi_gate.py)"""
     assert len(CASES) >= 250 and all(CONTRACT[n] for n in CONTRACT)
     assert set(ENGINE_ENTRY_POINTS) == {n for n, c in CONTRACT.items() if c is ENGINE}
 

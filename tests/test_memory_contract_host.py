@@ -8,6 +8,7 @@ import re
 import pytest
 import torch
 
+from tests.capi_host import L  # noqa: F401  (the fixture)
 from tests.memcheck import ALIGN, POISONS, Arena, ContractViolation, Partial, Plain, bit_equal, same_under_all_poisons
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -141,53 +142,13 @@ def test_partially_written_output():
 
 
 # ---- coverage gate -------------------------------------------------------------------------------------------------------
-# Entry points that take a non-const pointer but write no device memory:
-EXEMPT = {
-    "sifsr_layer_table": "introspection: fills a HOST int array, no GPU touched",
-    "sifsr_model_workspace_regions": "introspection: fills a HOST size_t array, no GPU touched",
-    "sifsr_profile_read": "measurement hook: writes two HOST scalars after synchronising its events",
-    "sifsr_profile_read_slot": "measurement hook: writes two HOST scalars after synchronising its events",
-}
-
-
-def _writers():
-    """{name: [non-const pointer argument names]} from the header, parsed as sifsr._lib.parse_header does but keeping `const`;
-    the `stream` handle is not memory."""
-    text = open(os.path.join(ROOT, "include", "sifsr_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    out, n = {}, 0
-    for m in re.finditer(r"SIFSR_API\s+([\w\s]+?)\s+(\w+)\s*\(([^)]*)\)\s*;", text):
-        n += 1
-        ptrs = []
-        for a in m.group(3).split(","):
-            a = " ".join(a.split())
-            mm = re.match(r"(.+?)\s*(\w+)$", a)
-            if mm and "*" in mm.group(1) and "const" not in mm.group(1) and mm.group(2) != "stream":
-                ptrs.append(mm.group(2))
-        if ptrs:
-            out[m.group(2)] = ptrs
-    assert n >= 80 and len(out) >= 55, (n, len(out))
-    return out
-
-
-def test_every_writing_entry_point_has_a_contract_case():
-    from tests import test_memory_contract_gpu as T
-    writers = _writers()
+def test_every_writing_entry_point_has_a_contract_case(L):
+    """what the header's writers are; that each has a row in CONTRACT (or an exemption with its reason) is held for every header
+    family by tests/test_capi_gate.py"""
+    writers = L.writers("core")
+    assert len(L.declared("core")) >= 80 and len(writers) >= 55, (len(L.declared("core")), len(writers))
     assert writers["sifsr_bn_relu_bwd_coef"][0] == "g" and "workspace" in writers["sifsr_model_forward"]
     assert "sifsr_conv3x3_stat_blocks" not in writers and "sifsr_huber_bwd" in writers
-    covered = set(T.CONTRACT)
-    for name in EXEMPT:
-        assert name in writers and name not in covered, name      # the exemption list stays minimal and current
-    missing = sorted(set(writers) - covered - set(EXEMPT))
-    assert not missing, f"no memory-contract case for {missing}: add a row to CONTRACT in tests/test_memory_contract_gpu.py"
-    stale = sorted(covered - set(writers))
-    assert not stale, f"CONTRACT rows for entry points the header does not declare as writers: {stale}"
-    for name, cases in T.CONTRACT.items():
-        assert len(cases) >= 1, name
-    # the model entry points are exercised through the engine module; its rows must name that module's cases
-    src = open(os.path.join(ROOT, "tests", "test_workspace_poison_gpu.py")).read()
-    for name in T.ENGINE_ENTRY_POINTS:
-        assert name in covered and f'"{name}"' in src, name
 
 
 def test_new_test_sources_hold_no_barred_instruction_names():

@@ -2,7 +2,7 @@
 flush to each raster edge, merged by a normalised feathered blend on the device.
 
   * the memory contract of the two writing entry points, in the guarded, poisoned arena of tests/memcheck.py (CONTRACT below is
-    the table tests/test_mosaic_host.py checks against the header),
+    the table tests/test_capi_gate.py checks against the header),
   * the defaults reproduce the non-overlapping path bit for bit,
   * every tile's network input is bit-identical to the existing kernel's for the same block,
   * the blend alone against its formula (partition of unity, continuity, a float64 NumPy restatement, coverage),
@@ -16,26 +16,14 @@ import torch
 
 from oracle import sif_oracle as O
 from tests.conftest import rel_err
-from tests.memcheck import Arena, Plain, bit_equal, same_under_all_poisons
-from tests.test_memory_contract_gpu import K, S
+from tests.contract import L, S, run_contract, sifsr  # noqa: F401  (L and sifsr are the fixtures)
+from tests.memcheck import bit_equal
 from tests.test_model_gpu import normalised_per_image_err
 
 pytestmark = pytest.mark.gpu
 STATS = {"mean_lst": 307.2378, "std_lst": 5.5698, "mean_ndvi": 0.6452, "std_ndvi": 0.1683}
 UNIT = {"mean_lst": 0.0, "std_lst": 1.0, "mean_ndvi": 0.0, "std_ndvi": 1.0}
 SHAPE_ERR = 1001
-
-
-@pytest.fixture(scope="module")
-def sifsr():
-    import sifsr as pkg
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return pkg
-
-
-@pytest.fixture(scope="module")
-def L(sifsr):
-    return sifsr._lib
 
 
 def origins(n, win, overlap, cover):
@@ -103,24 +91,11 @@ CONTRACT = {"sifsrx_tiles_prepare": tiles_prepare(), "sifsrx_tiles_blend": tiles
 CASES = [(name, i) for name, cases in CONTRACT.items() for i in range(len(cases))]
 
 
-def _execute(L, A, name, idx):
-    k = K(A, L, seed=sum(map(ord, name)) * 131 + idx)
-    call, outs = CONTRACT[name][idx](k)
-    torch.cuda.synchronize()
-    call()
-    torch.cuda.synchronize()
-    A.check()                                           # no guard byte and no const input (sr, lst, ndvi) changed
-    return {n: v.clone() for n, v in outs.items()}
-
-
 @pytest.mark.parametrize("name,idx", CASES, ids=[f"{n[7:]}-{i}" for n, i in CASES])
 def test_memory_contract(L, name, idx):
     """x / out fully written (NaN-free under the NaN poison, bit-identical under every poison), inputs untouched, nothing outside
     the buffers written, and the same bits on ordinary allocations."""
-    first = same_under_all_poisons(lambda p: _execute(L, Arena("cuda", poison=p), name, idx))
-    plain = _execute(L, Plain("cuda"), name, idx)
-    for n, v in first.items():
-        assert bit_equal(v, plain[n]), f"{n}: the arena run and the ordinary-allocation run differ"
+    run_contract(L, CONTRACT[name][idx], seed=sum(map(ord, name)) * 131 + idx)
 
 
 # ---- 2. defaults unchanged -----------------------------------------------------------------------------------------------

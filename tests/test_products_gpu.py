@@ -8,7 +8,7 @@
   * edge cases: nothing accepted (outputs untouched), everything accepted, two granules in turn = two single runs, a patch of a
     granule = the patch of its own cut-out raster, bit for bit,
   * the memory contract of every entry point in the guarded, poisoned arena of tests/memcheck.py (CONTRACT below is the table
-    tests/test_products_host.py checks against the header): rows past n_accepted keep their initial content,
+    tests/test_capi_gate.py checks against the header): rows past n_accepted keep their initial content,
   * the argument errors, and the way into the training loop: `loader`, one `train_epoch`, `predict_granule` on `decode`.
 
 Every comparison of kernel output is for equality; nothing here has a tolerance taken from what the kernels give."""
@@ -17,8 +17,8 @@ import pytest
 import torch
 
 from tests import products_reference as R
-from tests.memcheck import Arena, Partial, Plain, bit_equal, same_under_all_poisons
-from tests.test_memory_contract_gpu import K, S
+from tests.contract import L, S, dev, run_contract, sifsr  # noqa: F401  (L and sifsr are the fixtures)
+from tests.memcheck import Partial, bit_equal
 from tests.test_products_host import CONFIGS, check_statistics, golden  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
@@ -29,25 +29,9 @@ WS = 64
 
 
 @pytest.fixture(scope="module")
-def sifsr():
-    import sifsr as pkg
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return pkg
-
-
-@pytest.fixture(scope="module")
 def P(sifsr):
     from sifsr import products
     return products
-
-
-@pytest.fixture(scope="module")
-def L(sifsr):
-    return sifsr._lib
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a)).cuda()                    # (a copy: the cases are read-only)
 
 
 def rasters(case):
@@ -300,37 +284,12 @@ CONTRACT = _contract()
 CASES = [(name, i) for name, cases in CONTRACT.items() for i in range(len(cases))]
 
 
-def _execute(L, A, name, idx):
-    k = K(A, L, seed=sum(map(ord, name)) * 131 + idx)
-    call, outs = CONTRACT[name][idx](k)
-    torch.cuda.synchronize()
-    call()
-    torch.cuda.synchronize()
-    A.check()                                           # no guard byte and no const input changed
-    res = {}
-    for n, v in outs.items():
-        if callable(v):
-            p = v()
-            res[n] = Partial(p.tensor.clone(), p.written, p.initial)
-        else:
-            res[n] = v.clone()
-    return res
-
-
 @pytest.mark.parametrize("name,idx", CASES, ids=[f"{n[7:]}-{i}" for n, i in CASES])
 def test_memory_contract(L, name, idx):
     """every output written where the header says and nowhere else -- NaN-free under the NaN poison, bit-identical under every
     poison, rows past n_accepted still holding their poison --, inputs untouched, nothing outside the buffers written, and the same
     bits on ordinary allocations."""
-    first = same_under_all_poisons(lambda p: _execute(L, Arena("cuda", poison=p, capacity=64 << 20), name, idx))
-    plain = _execute(L, Plain("cuda"), name, idx)
-    for n, v in first.items():
-        other = plain[n]
-        if isinstance(other, Partial):
-            w = other.written.to(other.tensor.device).expand_as(other.tensor)
-            other = other.tensor.clone()
-            other[~w] = 0
-        assert bit_equal(v, other), f"{n}: the arena run and the ordinary-allocation run differ"
+    run_contract(L, CONTRACT[name][idx], seed=sum(map(ord, name)) * 131 + idx, capacity=64 << 20)
 
 
 # ---- 4. argument errors -------------------------------------------------------------------------------------------------------

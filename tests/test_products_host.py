@@ -6,23 +6,20 @@
     sha256 of every accepted patch, the 60/40 labels and statistics.json,
   * `MinedPatches.assign_split` / `.statistics` (host code: Chan merge of per-patch moments) on the restatement's patches give the
     golden labels and statistics; `MinedDataset` keeps the ModisDatasetB contract,
-  * the gate of include/sifsr_products.h, restated from tests/test_baselines_host.py for the `sifsrp_` entry points: the exported
-    symbols are exactly the declared ones, none falls under the other headers' export checks, every entry point that can write
-    through a pointer has a memory-contract case in tests/test_products_gpu.py.
+  * the pins of include/sifsr_products.h for the `sifsrp_` entry points (the gate itself is tests/test_capi_gate.py): the declared
+    names, every entry point that can write through a pointer has a memory-contract case in tests/test_products_gpu.py.
 
 Bounds.  Statistics: maxi / mini exactly; means and standard deviations to 1e-12 relative -- Chan merging of 500 per-patch
 float64 moments against np.mean / np.std of the concatenation differs by 7.6e-16 / 5.9e-16, while a one-pass E[x^2] - E[x]^2 loses
 about (300 / 5)^2 = 3600 times that."""
-import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import products_reference as R
+from tests.capi_host import L  # noqa: F401  (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONFIGS = [(ci, m, vi) for ci in range(len(R.CASES)) for m in (0, 1) for vi in range(len(R.COVERAGES))]
@@ -32,16 +29,6 @@ STAT_KEYS = ("maxi", "mini", "mean_lst", "std_lst", "mean_ndvi", "std_ndvi")
 @pytest.fixture(scope="module")
 def golden():
     return np.load(os.path.join(ROOT, "tests", "golden", "golden_products_v1.npz"))
-
-
-@pytest.fixture(scope="module")
-def L():
-    import sifsr  # noqa: F401
-    from sifsr import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib
 
 
 def check_statistics(got, want):
@@ -186,45 +173,11 @@ def test_public_interface():
         P.PatchMiner().add(z, torch.zeros((256, 256), dtype=torch.int16), torch.zeros((256, 256), dtype=torch.int16))
 
 
-# ---- the gate, restated for include/sifsr_products.h --------------------------------------------------------------------------
-def _declarations():
-    """{name: [non-const pointer argument names]} of every SIFSR_API declaration of the header; the `stream` handle is not memory."""
-    text = open(os.path.join(ROOT, "include", "sifsr_products.h")).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    out = {}
-    for m in re.finditer(r"SIFSR_API\s+([\w\s]+?)\s+(\w+)\s*\(([^)]*)\)\s*;", text):
-        ptrs = []
-        for a in m.group(3).split(","):
-            a = " ".join(a.split())
-            mm = re.match(r"(.+?)\s*(\w+)$", a)
-            if mm and "*" in mm.group(1) and "const" not in mm.group(1) and mm.group(2) != "stream":
-                ptrs.append(mm.group(2))
-        out[m.group(2)] = ptrs
-    return out
-
-
-def test_exported_product_symbols_are_the_declared_ones(L):
-    names = L.declared_product_symbols()
-    assert set(names) == set(_declarations()) and len(names) == 4
-    assert all(n.startswith("sifsrp_") and "sifsr_" not in n for n in names)
-    handle = ctypes.CDLL(L.LIB_PATH)
-    assert not [n for n in names if not hasattr(handle, n)]
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("sifsrp_")}
-    assert exported == set(names), exported ^ set(names)
-    others = set(L.declared_symbols()) | set(L.declared_extension_symbols()) | set(L.declared_baseline_symbols())
-    assert not set(names) & others
-    assert all(hasattr(L.lib(), n) for n in names)
-    assert L.call("sifsr_abi_version") == 3
-
-
+# ---- the pins of include/sifsr_products.h (the gate itself is tests/test_capi_gate.py) -----------------------------------------
 def test_every_writing_product_entry_point_has_a_contract_case(L):
     from tests import test_products_gpu as T
-    writers = {n: p for n, p in _declarations().items() if p}
+    assert len(L.declared("products")) == 4
+    writers = L.writers("products")
     assert writers == {"sifsrp_decode": ["lst_k", "ndvi"], "sifsrp_census": ["counts"], "sifsrp_select": ["index", "n_accepted"],
                        "sifsrp_gather": ["lst", "ndvi", "moments"]}
-    missing = sorted(set(writers) - set(T.CONTRACT))
-    assert not missing, f"no memory-contract case for {missing}: add a row to CONTRACT in tests/test_products_gpu.py"
-    stale = sorted(set(T.CONTRACT) - set(writers))
-    assert not stale, f"CONTRACT rows for entry points the header does not declare as writers: {stale}"
     assert all(len(cases) >= 3 for cases in T.CONTRACT.values())

@@ -6,7 +6,7 @@
     in the images = the explicit mask; what an invalid pixel holds changes no bit; the edge counts (nothing valid, one 9 x 9
     block, a block in the corner); lists, determinism, one hipGraph capture,
   * the memory contract of the two writing entry points in the guarded, poisoned arena of tests/memcheck.py (CONTRACT below is the
-    table tests/test_scores_host.py checks against the header),
+    table tests/test_capi_gate.py checks against the header),
   * train-time pair: B = 2 at (40, 24), (64, 64), (100, 36), both scales, three masks, within the f1 tolerances of
     tests/test_pipeline_gpu.py::test_psnr_ssim; every byte valid = psnr_ssim bit for bit; nothing valid = NaN,
   * the epoch keyword."""
@@ -16,26 +16,14 @@ import torch
 
 from tests import eval_reference as E
 from tests import scores_reference as R
-from tests.memcheck import Arena, Plain, bit_equal, same_under_all_poisons
+from tests.contract import L, S, run_contract, sifsr  # noqa: F401  (L and sifsr are the fixtures)
+from tests.memcheck import bit_equal
 from tests.test_eval_metrics_gpu import check_row
-from tests.test_memory_contract_gpu import K, S
 
 pytestmark = pytest.mark.gpu
 U8, I32, F64 = torch.uint8, torch.int32, torch.float64
 WORKSPACE_ERR = 1003
 G_OUT = 0xFFFFFFFF
-
-
-@pytest.fixture(scope="module")
-def sifsr():
-    import sifsr as pkg
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return pkg
-
-
-@pytest.fixture(scope="module")
-def L(sifsr):
-    return sifsr._lib
 
 
 def dev(x):
@@ -260,24 +248,11 @@ CONTRACT = {"sifsrv_eval_metrics": [eval_case(hw) for hw in ((16, 16), (41, 57),
 CASES = [(name, i) for name, cases in CONTRACT.items() for i in range(len(cases))]
 
 
-def _execute(L, A, name, idx):
-    k = K(A, L, seed=sum(map(ord, name)) * 131 + idx)
-    call, outs = CONTRACT[name][idx](k)
-    torch.cuda.synchronize()
-    call()
-    torch.cuda.synchronize()
-    A.check()                                           # no guard byte and no const input changed
-    return {n: v.clone() for n, v in outs.items()}
-
-
 @pytest.mark.parametrize("name,idx", CASES, ids=[f"{n[7:]}-{i}" for n, i in CASES])
 def test_memory_contract(L, name, idx):
     """every output written in full and nowhere else -- NaN-free under the NaN poison, bit-identical under every poison (the
     poisoned scratch included) --, const inputs untouched, and the same bits on ordinary allocations."""
-    first = same_under_all_poisons(lambda p: _execute(L, Arena("cuda", poison=p, capacity=64 << 20), name, idx))
-    plain = _execute(L, Plain("cuda"), name, idx)
-    for n, v in first.items():
-        assert bit_equal(v, plain[n]), f"{n}: the arena run and the ordinary-allocation run differ"
+    first = run_contract(L, CONTRACT[name][idx], seed=sum(map(ord, name)) * 131 + idx, capacity=64 << 20)
     if name == "sifsrv_eval_metrics":
         assert (first["counts5"] > 0).all()
 

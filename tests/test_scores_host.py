@@ -5,15 +5,13 @@
   * the cases of the GPU tolerance tests have enough terms: every one of the five counts of every blob image is >= 300, and the
     smallest are the ones the masks were chosen for; the edge cases have the counts they are planted for,
   * the train-time restatement with an all-ones mask is the oracle's psnr_skimage / ssim_skimage,
-  * the gate of include/sifsr_scores.h, restated from tests/test_masked_host.py for the `sifsrv_` entry points: the exported symbols
-    are exactly the declared ones, none falls under the other headers, every entry point that can write through a pointer has a
-    memory-contract case in tests/test_scores_gpu.py, scratch sizes and error codes through the host-only paths,
+  * the pins of include/sifsr_scores.h for the `sifsrv_` entry points (the gate itself is tests/test_capi_gate.py): the declared
+    names, every entry point that can write through a pointer has a memory-contract case in tests/test_scores_gpu.py, scratch sizes
+    and error codes through the host-only paths,
   * the public names exist with the defaults that leave every existing call as it was."""
 import ctypes
 import inspect
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,19 +20,10 @@ import torch
 from oracle import sif_oracle as O
 from tests import eval_reference as E
 from tests import scores_reference as R
+from tests.capi_host import L  # noqa: F401  (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "golden_eval_v1.npz")
-
-
-@pytest.fixture(scope="module")
-def L():
-    import sifsr  # noqa: F401
-    from sifsr import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib
 
 
 def same_bits(x, y):
@@ -130,45 +119,13 @@ def test_train_time_masks(hw):
         assert R.psnr_ssim(p, t, np.zeros_like(v), scale)[2] == (0, 0)
 
 
-# ---- 2. the gate, restated for include/sifsr_scores.h ----------------------------------------------------------------------------
-def _declarations():
-    """{name: [non-const pointer argument names]} of every SIFSR_API declaration of the header; the `stream` handle is not memory."""
-    text = open(os.path.join(ROOT, "include", "sifsr_scores.h")).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    out = {}
-    for m in re.finditer(r"SIFSR_API\s+([\w\s]+?)\s+(\w+)\s*\(([^)]*)\)\s*;", text):
-        ptrs = []
-        for a in m.group(3).split(","):
-            a = " ".join(a.split())
-            mm = re.match(r"(.+?)\s*(\w+)$", a)
-            if mm and "*" in mm.group(1) and "const" not in mm.group(1) and mm.group(2) != "stream":
-                ptrs.append(mm.group(2))
-        out[m.group(2)] = ptrs
-    return out
-
-
-def test_exported_score_symbols_are_the_declared_ones(L):
-    names = L.declared_score_symbols()
-    assert set(names) == set(_declarations())
-    assert names == ["sifsrv_eval_metrics", "sifsrv_eval_metrics_scratch_bytes", "sifsrv_psnr_ssim", "sifsrv_psnr_ssim_scratch_bytes"]
-    assert all(n.startswith("sifsrv_") and "sifsr_" not in n for n in names)
-    handle = ctypes.CDLL(L.LIB_PATH)
-    assert not [n for n in names if not hasattr(handle, n)]
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("sifsrv_")}
-    assert exported == set(names), exported ^ set(names)
-    others = (set(L.declared_symbols()) | set(L.declared_extension_symbols()) | set(L.declared_baseline_symbols())
-              | set(L.declared_product_symbols()) | set(L.declared_gap_symbols()) | set(L.declared_masked_symbols()))
-    assert not set(names) & others
-    assert all(hasattr(L.lib(), n) for n in names)
-    assert L.call("sifsr_abi_version") == 3
-
-
+# ---- 2. the pins of include/sifsr_scores.h (the gate itself is tests/test_capi_gate.py) -----------------------------------------
 def test_every_writing_score_entry_point_has_a_contract_case(L):
     from tests import test_scores_gpu as T
-    writers = {n: p for n, p in _declarations().items() if p}
+    names, writers = L.declared("scores"), L.writers("scores")
+    assert names == ["sifsrv_eval_metrics", "sifsrv_eval_metrics_scratch_bytes", "sifsrv_psnr_ssim", "sifsrv_psnr_ssim_scratch_bytes"]
     assert writers == {"sifsrv_eval_metrics": ["scratch", "out8", "counts5"], "sifsrv_psnr_ssim": ["scratch", "out2", "counts2"]}
-    assert all(_declarations()[n] == [] for n in ("sifsrv_eval_metrics_scratch_bytes", "sifsrv_psnr_ssim_scratch_bytes"))
+    assert all(n not in writers for n in ("sifsrv_eval_metrics_scratch_bytes", "sifsrv_psnr_ssim_scratch_bytes"))
     assert sorted(T.CONTRACT) == sorted(writers)
     assert all(len(cases) >= 3 for cases in T.CONTRACT.values())
 
@@ -232,4 +189,4 @@ def test_public_interface():
         metrics.masked_aster_metrics(z, z)
     with pytest.raises(sifsr.SifsrError):
         metrics.masked_psnr_ssim(z, z, torch.ones((1, 1, 4, 4), dtype=torch.uint8))
-    assert os.path.samefile(sifsr._lib.SCORES_HEADER, os.path.join(ROOT, "include", "sifsr_scores.h"))
+    assert os.path.samefile(sifsr._lib.header_path("scores"), os.path.join(ROOT, "include", "sifsr_scores.h"))

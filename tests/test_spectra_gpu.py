@@ -19,26 +19,14 @@ import torch
 
 from oracle import sif_oracle as O
 from tests.golden.make_golden_spectra import CASES, SCORES, fourier_case
-from tests.memcheck import Arena, Plain, bit_equal, same_under_all_poisons
-from tests.test_memory_contract_gpu import K, S
+from tests.contract import L, S, execute, run_contract, sifsr  # noqa: F401  (L and sifsr are the fixtures)
+from tests.memcheck import Plain, bit_equal
 
 pytestmark = pytest.mark.gpu
 SHAPE_ERR, ARG_ERR, WORKSPACE_ERR = 1001, 1002, 1003
 DB_TOL = 2e-4
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = json.load(open(os.path.join(ROOT, "tests", "golden", "golden_spectra_v1.json")))
-
-
-@pytest.fixture(scope="module")
-def sifsr():
-    import sifsr as pkg
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return pkg
-
-
-@pytest.fixture(scope="module")
-def L(sifsr):
-    return sifsr._lib
 
 
 _IMAGES = {}
@@ -222,30 +210,19 @@ def spectra_case(i):
 CONTRACT = {"sifsrf_fft2_attenuation": [spectra_case(i) for i in range(len(CONTRACT_SHAPES))]}
 
 
-def _execute(L, A, idx):
-    k = K(A, L, seed=1977 + idx)
-    call, outs = CONTRACT["sifsrf_fft2_attenuation"][idx](k)
-    torch.cuda.synchronize()
-    call()
-    torch.cuda.synchronize()
-    A.check()                                           # no guard byte and no const input changed
-    return {n: v.clone() for n, v in outs.items()}
-
-
 @pytest.mark.parametrize("idx", range(len(CONTRACT_SHAPES)), ids=["%dx%dx%d-mag%d-spec%d" % s for s in CONTRACT_SHAPES])
 def test_memory_contract(L, idx):
     """mag and spectrum written in full and nowhere else -- bit-identical and NaN-free under every poison of the outputs and of the
     scratch buffer (the zero padding up to M, the filter spectra and the ring partials are written before they are read) --, img
     untouched, nothing outside the stated scratch bytes written, the same bits on ordinary allocations and with the other output
     absent, and the result is the oracle's."""
-    first = same_under_all_poisons(lambda p: _execute(L, Arena("cuda", poison=p, capacity=16 << 20), idx))
-    plain = _execute(L, Plain("cuda"), idx)
-    for n, v in first.items():
-        assert bit_equal(v, plain[n]), f"{n}: the arena run and the ordinary-allocation run differ"
+    cases = CONTRACT["sifsrf_fft2_attenuation"]
+    first = run_contract(L, cases[idx], seed=1977 + idx, capacity=16 << 20)
     B, H, W, want_mag, want_spec = CONTRACT_SHAPES[idx]
     x = contract_input(idx)
     if not (want_mag and want_spec):                    # an output does not depend on whether the other one was asked for
-        both = _execute(L, Plain("cuda"), CONTRACT_SHAPES.index((B, H, W, True, True)))
+        j = CONTRACT_SHAPES.index((B, H, W, True, True))
+        both = execute(L, Plain("cuda"), cases[j], seed=1977 + j)
         for n, v in first.items():
             assert bit_equal(v, both[n]), n
     for b in range(B):

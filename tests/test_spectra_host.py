@@ -2,40 +2,30 @@
 
   * tests/golden/golden_spectra_v1.json (the reference's compute_2D_attenuation_spectra and get_* on the rectangles of
     make_golden_spectra.CASES, written where the reference is) against the oracle: spectra at 1e-6 dB, as the generator asserted,
-  * the score algebra of sifsr.spectra (the get_* functions of sifsr.fourier, RMSE_ATT over the whole spectrum, summary_rows) against
+  * the score algebra of sifsr.spectra (the get_* functions of sifsr.fourier, RMSE_ATT over the whole spectrum, summary_rows)
+    against
     the golden and against closed forms written out here in NumPy: the order statistic with linear interpolation that np.percentile
     and DataFrame.quantile share, and both standard deviations,
-  * the gate of include/sifsr_spectra.h, restated from tests/test_conserve_host.py for the `sifsrf_` entry points: the exported symbols
-    are exactly the declared ones, none falls under the other headers, the writing entry point has memory-contract cases in
-    tests/test_spectra_gpu.py, the scratch size and the error codes through the host-only paths,
+  * the pins of include/sifsr_spectra.h for the `sifsrf_` entry points (the gate itself is tests/test_capi_gate.py): the declared
+    names, the writing entry point has memory-contract cases in tests/test_spectra_gpu.py, the scratch size and the error codes
+    through the host-only paths,
   * the public names."""
 import ctypes
 import inspect
 import json
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import sif_oracle as O
+from tests.capi_host import L  # noqa: F401  (the fixture)
 from tests.golden.make_golden_spectra import CASES, SCORES, fourier_case
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = json.load(open(os.path.join(ROOT, "tests", "golden", "golden_spectra_v1.json")))
 TABLE = [(41, 41), (47, 53), (33, 65), (63, 31), (48, 100), (100, 256), (256, 100), (213, 198), (1000, 48), (1024, 36)]
-
-
-@pytest.fixture(scope="module")
-def L():
-    import sifsr  # noqa: F401
-    from sifsr import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib
 
 
 # ---- 1. the golden file ----------------------------------------------------------------------------------------------------------
@@ -118,51 +108,21 @@ def test_summary_rows(n):
             bad()
 
 
-# ---- 3. the gate, restated for include/sifsr_spectra.h ---------------------------------------------------------------------------
-def _declarations():
-    """{name: [non-const pointer argument names]} of every SIFSR_API declaration of the header; the `stream` handle is not memory."""
-    text = open(os.path.join(ROOT, "include", "sifsr_spectra.h")).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    out = {}
-    for m in re.finditer(r"SIFSR_API\s+([\w\s]+?)\s+(\w+)\s*\(([^)]*)\)\s*;", text):
-        ptrs = []
-        for a in m.group(3).split(","):
-            a = " ".join(a.split())
-            mm = re.match(r"(.+?)\s*(\w+)$", a)
-            if mm and "*" in mm.group(1) and "const" not in mm.group(1) and mm.group(2) != "stream":
-                ptrs.append(mm.group(2))
-        out[m.group(2)] = ptrs
-    return out
-
-
-def test_exported_spectra_symbols_are_the_declared_ones(L):
-    names = L.declared_spectra_symbols()
-    assert set(names) == set(_declarations())
+# ---- 3. the pins of include/sifsr_spectra.h (the gate itself is tests/test_capi_gate.py) ----------------------------------------
+def test_the_signatures_are_the_existing_entry_points(L):
+    names = L.declared("spectra")
     assert names == ["sifsrf_fft2_attenuation", "sifsrf_fft2_attenuation_scratch_bytes"]
-    assert all(n.startswith("sifsrf_") and "sifsr_" not in n for n in names)
-    handle = ctypes.CDLL(L.LIB_PATH)
-    assert not [n for n in names if not hasattr(handle, n)]
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("sifsrf_")}
-    assert exported == set(names), exported ^ set(names)
-    others = (set(L.declared_symbols()) | set(L.declared_extension_symbols()) | set(L.declared_baseline_symbols())
-              | set(L.declared_product_symbols()) | set(L.declared_gap_symbols()) | set(L.declared_masked_symbols())
-              | set(L.declared_score_symbols()) | set(L.declared_lpips_symbols()) | set(L.declared_conserve_symbols())
-              | set(L.declared_dms_symbols()))
-    assert not set(names) & others
-    assert all(hasattr(L.lib(), n) for n in names)
-    assert L.call("sifsr_abi_version") == 3
     # the two signatures differ from the existing entry points' in the name alone
-    old, new = L.parse_header(), L.parse_header(L.SPECTRA_HEADER)
+    old, new = L.parse_header(), L.parse_header(L.header_path("spectra"))
     for n in names:
         assert new[n] == old[n.replace("sifsrf_", "sifsr_")]
+        assert [(a.pointer, a.const) for a in new[n][1]] == [(a.pointer, a.const) for a in old[n.replace("sifsrf_", "sifsr_")][1]]
 
 
 def test_the_writing_entry_point_has_contract_cases(L):
     from tests import test_spectra_gpu as T
-    writers = {n: p for n, p in _declarations().items() if p}
+    writers = L.writers("spectra")
     assert writers == {"sifsrf_fft2_attenuation": ["scratch", "mag", "spectrum"]}
-    assert _declarations()["sifsrf_fft2_attenuation_scratch_bytes"] == []
     assert sorted(T.CONTRACT) == sorted(writers)
     assert {s[:3] for s in T.CONTRACT_SHAPES} == {(2, 41, 53), (1, 100, 256), (1, 33, 65)}
     # every shape with both outputs, with each one alone
@@ -221,7 +181,7 @@ def test_public_interface():
     assert sig(spectra.fft2_magnitude) == [("img", E_)] and sig(spectra.attenuation_spectra) == [("img", E_)]
     assert sig(spectra.spectral_scores) == [("aster", E_), ("bicubic", E_), ("predictions", E_)]
     assert sig(spectra.summary_rows) == [("table", E_), ("ddof", E_)]
-    assert os.path.samefile(sifsr._lib.SPECTRA_HEADER, os.path.join(ROOT, "include", "sifsr_spectra.h"))
+    assert os.path.samefile(sifsr._lib.header_path("spectra"), os.path.join(ROOT, "include", "sifsr_spectra.h"))
     z = torch.zeros((41, 53))
     for call in (lambda: spectra.fft2_magnitude(z), lambda: spectra.attenuation_spectra([z, torch.zeros((64, 64))]),
                  lambda: spectra.spectral_scores(z, z, z[None]), lambda: spectra.spectral_scores([z], [z], [[z, z]])):
