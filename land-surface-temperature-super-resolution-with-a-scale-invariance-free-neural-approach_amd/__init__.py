@@ -34,6 +34,9 @@ Drop-in surface (SURVEY.md §8 b):
   adapt.frozen_bn / input_gradient / tile_targets / adapt_granule, ModelB_2.bn_frozen  <- no counterpart: fine-tuning a trained
                                        model on the granule it is about to predict -- BatchNorm backward with frozen running statistics,
                                        the gradient with respect to the network input, loss targets of active tiles (include/sifsr_adapt.h)
+  sensor.downscale / lowpass / lr_shape / sif_loss / train_step  <- utils.py:1671-1706, :1833-1860 at any factor, as autograd ops
+                                       (the adjoint of the banded sensor operator and the reflect-border MTF low-pass, forward
+                                       and adjoint), the SIF loss and a training step at any ratio (include/sifsr_sensor.h)
   products.decode / PatchMiner / MinedPatches, dataset.MinedDataset  <- process_modis.py:38-335, data_preparation.py:32-102
                                        (raw granule arrays -> patches + statistics.json, on device)
 
@@ -44,7 +47,7 @@ and registers ``sifsr`` / ``sifsr.<submodule>`` as aliases of the same module ob
 import importlib
 import sys
 
-_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "degrade", "predict", "baselines", "products", "lpips", "adapt")
+_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "degrade", "predict", "baselines", "products", "lpips", "adapt", "sensor")
 for _m in _SUBMODULES:
     importlib.import_module(__name__ + "." + _m)
 

@@ -13,7 +13,19 @@
 //  * degrade_cols_kernel    a lane owns one output; it walks K consecutive entries of the intermediate row, 1 / factor of the
 //    first pass' data.  Validity, fill value and the single rounding to fp32 happen here.
 // No LDS, no atomics, no allocation, no host synchronisation; nothing depends on the order in which workgroups run.
+//
+// The differentiable half (include/sifsr_sensor.h): dx = Ry^T . dout . Rx as a GATHER over the same tables, and
+// the reflect-border low-pass of get_output_ftm at any half width through the same passes with another table.
+//  * lowpass_table_kernel   the table of L: output o has 2 hw + 1 weights over [max(0, o - hw), ..], both reflections folded in.
+//  * range_kernel           one thread per INPUT index of an axis: the run [o_lo, o_hi] of outputs whose stencil holds it, by
+//    bisection of the stencil ends the table kernel stored (both are non-decreasing in o).  An empty run means a zero gradient.
+//  * adjoint_cols_kernel    the small pass first: a lane owns input column j of one OUTPUT row and sums its run of output columns
+//    (validity is applied here) into the (B, oh, w) float64 intermediate; writes are coalesced.
+//  * adjoint_rows_kernel    the large pass: a wave owns 64 consecutive columns of ONE input row; its run of output rows and their
+//    weights are wave-uniform (scalar loads), the intermediate is read coalesced.  Rounds to fp32 once.
+// The runs have no compile-time bound (52 outputs over one pixel at factor 1.25 with hkw 16): both passes loop over the stored run.
 #include "../../include/sifsr_degrade.h"
+#include "../../include/sifsr_sensor.h"
 
 #include <math.h>
 
@@ -169,6 +181,104 @@ __global__ __launch_bounds__(256) void degrade_cols_kernel(const double* __restr
   if (out_valid != nullptr) out_valid[dst] = (unsigned char)ok;
 }
 
+// ---- the differentiable half (include/sifsr_sensor.h) ----
+// one thread per weight of an axis, in the layouts of degrade_table_kernel with K = 2 hw + 1: row weights [output][tap], column
+// weights [tap][output]; tap k of output o is pixel max(0, o - hw) + k.  A.count == A.n.
+__global__ __launch_bounds__(256) void lowpass_table_kernel(const Psf p, const Axis ay, const Axis ax, double* __restrict__ wy,
+                                                            double* __restrict__ wx, int4* __restrict__ my, int4* __restrict__ mx) {
+#pragma clang fp contract(off)
+  const bool rows = blockIdx.y == 0;
+  const Axis A = rows ? ay : ax;
+  const int hw = p.hw, K = 2 * hw + 1, n = A.n;
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= n * K) return;
+  const int o = rows ? e / K : e % n, k = rows ? e % K : e / n;
+  const int start = max(o - hw, 0), j = start + k;
+  double w = 0.0;
+  if (j < n) {
+    // the reflected positions that hold pixel j: itself, its mirror at the low edge, its mirror at the high edge (hw <= n - 1)
+    const int cand[3] = {j, -j, 2 * (n - 1) - j};
+    const bool use[3] = {true, j >= 1, j <= n - 2};
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      const int d = cand[m] - o;
+      if (use[m] && d >= -hw && d <= hw) w += p.g[d + hw];
+    }
+  }
+  (rows ? wy : wx)[e] = w;
+  if (k == 0) (rows ? my : mx)[o] = make_int4(start, start, min(o + hw, n - 1), 0);
+}
+
+// one thread per input index of an axis (blockIdx.y: 0 rows, 1 columns): the outputs o with lo(o) <= i <= hi(o).  lo and hi are
+// non-decreasing in o, so these are [first o with hi(o) >= i, last o with lo(o) <= i]; the run is empty when the first is past the
+// last.  Whatever the table holds, 0 <= first <= count and -1 <= last <= count - 1.
+__global__ __launch_bounds__(256) void range_kernel(const int4* __restrict__ my, const int4* __restrict__ mx, int2* __restrict__ ry,
+                                                    int2* __restrict__ rx, int h, int w, int oh, int ow) {
+  const bool rows = blockIdx.y == 0;
+  const int n = rows ? h : w, count = rows ? oh : ow;
+  const int4* m = rows ? my : mx;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  int a = 0, b = count;                                    // first o in [0, count] with hi(o) >= i
+  while (a < b) {
+    const int c = (a + b) >> 1;
+    if (m[c].z >= i) b = c; else a = c + 1;
+  }
+  const int first = a;
+  a = 0, b = count;                                        // first o in [0, count] with lo(o) > i
+  while (a < b) {
+    const int c = (a + b) >> 1;
+    if (m[c].y > i) b = c; else a = c + 1;
+  }
+  (rows ? ry : rx)[i] = make_int2(first, a - 1);
+}
+
+// grid (ceil(w / BX), ceil(oh / BY), B), 256 threads: lane = input column j, wave = output row oy.
+// tmp[b, oy, j] = sum over ox in the run of j of wx[ox][j - start(ox)] * dout[b, oy, ox], ascending ox
+__global__ __launch_bounds__(256) void adjoint_cols_kernel(const float* __restrict__ dout, const unsigned char* __restrict__ out_valid,
+                                                           const double* __restrict__ wx, const int4* __restrict__ mx,
+                                                           const int2* __restrict__ rx, double* __restrict__ tmp, int w, int oh,
+                                                           int ow, int K) {
+  const int oy = __builtin_amdgcn_readfirstlane(blockIdx.y * BY + (threadIdx.x >> 6));
+  const int j = blockIdx.x * BX + (threadIdx.x & 63);
+  if (oy >= oh || j >= w) return;
+  const int2 r = rx[j];
+  const size_t row = ((size_t)blockIdx.z * oh + oy) * ow;
+  const float* src = dout + row;
+  double acc = 0.0;
+  for (int ox = r.x; ox <= r.y; ++ox) {
+    const int k = j - mx[ox].x;                             // the tap of output ox that lies over pixel j
+    if (k < 0 || k >= K) continue;                          // (never, while the stencil lies inside the window)
+    const double wgt = wx[(size_t)k * ow + ox];
+    const bool counted = out_valid == nullptr || out_valid[row + ox] != 0;
+    const double v = (double)src[ox];
+    acc = (counted && wgt != 0.0) ? fma(wgt, v, acc) : acc;  // what lies under a zero weight or an uncounted output is not used
+  }
+  tmp[((size_t)blockIdx.z * oh + oy) * w + j] = acc;
+}
+
+// grid (ceil(w / BX), ceil(h / BY), B), 256 threads: wave v of the workgroup owns INPUT row blockIdx.y * BY + v.
+// dx[b, i, j] = sum over oy in the run of i of wy[oy][i - start(oy)] * tmp[b, oy, j], ascending oy
+__global__ __launch_bounds__(256) void adjoint_rows_kernel(const double* __restrict__ tmp, const double* __restrict__ wy,
+                                                           const int4* __restrict__ my, const int2* __restrict__ ry,
+                                                           float* __restrict__ dx, int h, int w, int oh, int K) {
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.y * BY + (threadIdx.x >> 6));
+  const int col = blockIdx.x * BX + (threadIdx.x & 63);
+  if (i >= h || col >= w) return;
+  const int2 r = ry[i];
+  const double* src = tmp + (size_t)blockIdx.z * oh * w + col;
+  double acc = 0.0;
+#pragma unroll 4
+  for (int oy = r.x; oy <= r.y; ++oy) {
+    const int k = i - my[oy].x;
+    if (k < 0 || k >= K) continue;                          // (never, while the stencil lies inside the window)
+    const double wgt = wy[(size_t)oy * K + k];
+    const double v = src[(size_t)oy * w];
+    acc = wgt != 0.0 ? fma(wgt, v, acc) : acc;
+  }
+  dx[((size_t)blockIdx.z * h + i) * w + col] = (float)acc;
+}
+
 bool axis_of(int n, double factor, int hw, int crop, Axis* a) {
   if (n < hw + 1 || n > MAX_SIDE) return false;
   a->n = n;
@@ -201,6 +311,97 @@ bool plan_of(int B, int h, int w, double factor, int hkw, int crop, Plan* p) {
 
 bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
+Psf psf_of(double factor, double mtf, int hw) {
+  Psf psf;
+  const double pi = 3.14159265358979323846;
+  const double sigma = sqrt(-log(mtf) / 2.0) / (pi * (0.5 / factor));
+  double sum = 0.0;
+  for (int k = -hw; k <= hw; ++k) sum += (psf.g[k + hw] = exp(-((double)k * k) / (2.0 * sigma * sigma)));
+  for (int k = 0; k < 2 * MAX_HW + 1; ++k) psf.g[k] = k <= 2 * hw ? psf.g[k] / sum : 0.0;
+  psf.hw = hw;
+  psf.scale = (float)(1.0 / (1.0 / factor));
+  return psf;
+}
+
+// The adjoint's workspace: the forward's two weight tables and two stencil tables at the forward's offsets, then one run per input
+// index of each axis and the (B, oh, w) float64 intermediate.  `lowpass`: oh = h, ow = w, K = 2 hw + 1, no crop.
+struct AdjointPlan {
+  int hw, K, oh, ow;
+  Axis ay, ax;
+  size_t wy_off, wx_off, my_off, mx_off, ry_off, rx_off, tmp_off, bytes;
+};
+
+bool adjoint_plan_of(int B, int h, int w, double factor, int hkw, int crop, bool lowpass, AdjointPlan* a) {
+  if (lowpass) {                                           // the limits of plan_of but one: there is always an output
+    if (!(factor > 1.0 && factor <= 16.0) || hkw < 0 || B < 1 || B > MAX_BATCH) return false;
+    a->hw = hkw == 0 ? (int)ceil(factor) : hkw;
+    if (a->hw < 1 || a->hw > MAX_HW || h < a->hw + 1 || w < a->hw + 1 || h > MAX_SIDE || w > MAX_SIDE) return false;
+    a->ay = Axis{h, h + 2 * a->hw, h, 0};
+    a->ax = Axis{w, w + 2 * a->hw, w, 0};
+  } else {
+    Plan p;
+    if (!plan_of(B, h, w, factor, hkw, crop, &p)) return false;
+    a->hw = p.hw;
+    a->ay = p.ay;
+    a->ax = p.ax;
+  }
+  a->K = lowpass ? 2 * a->hw + 1 : 2 * a->hw + 4;
+  a->oh = a->ay.count;
+  a->ow = a->ax.count;
+  a->wy_off = 0;
+  a->wx_off = up16((size_t)a->oh * a->K * sizeof(double));
+  a->my_off = a->wx_off + up16((size_t)a->ow * a->K * sizeof(double));
+  a->mx_off = a->my_off + (size_t)a->oh * sizeof(int4);
+  a->ry_off = a->mx_off + (size_t)a->ow * sizeof(int4);
+  a->rx_off = a->ry_off + (size_t)h * sizeof(int2);
+  a->tmp_off = up16(a->rx_off + (size_t)w * sizeof(int2));
+  a->bytes = up16(a->tmp_off + (size_t)B * a->oh * w * sizeof(double));
+  return true;
+}
+
+struct AdjointBuffers {
+  double *wy, *wx, *tmp;
+  int4 *my, *mx;
+  int2 *ry, *rx;
+};
+
+AdjointBuffers buffers_of(void* workspace, const AdjointPlan& a) {
+  char* ws = static_cast<char*>(workspace);
+  AdjointBuffers b;
+  b.wy = reinterpret_cast<double*>(ws + a.wy_off);
+  b.wx = reinterpret_cast<double*>(ws + a.wx_off);
+  b.my = reinterpret_cast<int4*>(ws + a.my_off);
+  b.mx = reinterpret_cast<int4*>(ws + a.mx_off);
+  b.ry = reinterpret_cast<int2*>(ws + a.ry_off);
+  b.rx = reinterpret_cast<int2*>(ws + a.rx_off);
+  b.tmp = reinterpret_cast<double*>(ws + a.tmp_off);
+  return b;
+}
+
+int launch_table(const AdjointPlan& a, const AdjointBuffers& b, const Psf& psf, bool lowpass, hipStream_t s) {
+  const int most = (a.oh > a.ow ? a.oh : a.ow) * a.K;
+  if (lowpass)
+    hipLaunchKernelGGL(lowpass_table_kernel, dim3((most + 255) / 256, 2), dim3(256), 0, s, psf, a.ay, a.ax, b.wy, b.wx, b.my, b.mx);
+  else
+    hipLaunchKernelGGL(degrade_table_kernel, dim3((most + 255) / 256, 2), dim3(256), 0, s, psf, a.ay, a.ax, b.wy, b.wx, b.my, b.mx);
+  SIFSR_LAUNCH_CHECK();
+  return SIFSR_OK;
+}
+
+// range kernel, adjoint column pass, adjoint row pass: dx (B, h, w) from dout (B, oh, ow) over the tables in `b`
+int launch_adjoint(const AdjointPlan& a, const AdjointBuffers& b, const float* dout, const unsigned char* out_valid, float* dx, int B,
+                   int h, int w, hipStream_t s) {
+  hipLaunchKernelGGL(range_kernel, dim3(((h > w ? h : w) + 255) / 256, 2), dim3(256), 0, s, b.my, b.mx, b.ry, b.rx, h, w, a.oh, a.ow);
+  SIFSR_LAUNCH_CHECK();
+  const int gx = (w + BX - 1) / BX;
+  hipLaunchKernelGGL(adjoint_cols_kernel, dim3(gx, (a.oh + BY - 1) / BY, B), dim3(256), 0, s, dout, out_valid, b.wx, b.mx, b.rx, b.tmp, w,
+                     a.oh, a.ow, a.K);
+  SIFSR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(adjoint_rows_kernel, dim3(gx, (h + BY - 1) / BY, B), dim3(256), 0, s, b.tmp, b.wy, b.my, b.ry, dx, h, w, a.oh, a.K);
+  SIFSR_LAUNCH_CHECK();
+  return SIFSR_OK;
+}
+
 }  // namespace
 
 // ---- C ABI (include/sifsr_degrade.h) ----
@@ -226,15 +427,7 @@ int sifsrs_degrade(const float* x, const unsigned char* valid, float* out, unsig
   if (!plan_of(B, h, w, factor, hkw, crop, &p) || !(mtf > 0.0 && mtf < 1.0)) return SIFSR_ERR_SHAPE;
   if (workspace_bytes < p.bytes) return SIFSR_ERR_WORKSPACE;
 
-  Psf psf;
-  const double pi = 3.14159265358979323846;
-  const double sigma = sqrt(-log(mtf) / 2.0) / (pi * (0.5 / factor));
-  double sum = 0.0;
-  for (int k = -p.hw; k <= p.hw; ++k) sum += (psf.g[k + p.hw] = exp(-((double)k * k) / (2.0 * sigma * sigma)));
-  for (int k = 0; k < 2 * MAX_HW + 1; ++k) psf.g[k] = k <= 2 * p.hw ? psf.g[k] / sum : 0.0;
-  psf.hw = p.hw;
-  psf.scale = (float)(1.0 / (1.0 / factor));
-
+  const Psf psf = psf_of(factor, mtf, p.hw);
   char* ws = static_cast<char*>(workspace);
   double* wy = reinterpret_cast<double*>(ws + p.wy_off);
   double* wx = reinterpret_cast<double*>(ws + p.wx_off);
@@ -253,4 +446,59 @@ int sifsrs_degrade(const float* x, const unsigned char* valid, float* out, unsig
                      p.oh, p.ow, p.K, valid != nullptr ? 1 : 0, fill_value);
   SIFSR_LAUNCH_CHECK();
   return SIFSR_OK;
+}
+
+// ---- C ABI (include/sifsr_sensor.h) ----
+size_t sifsrt_degrade_bwd_workspace_bytes(int B, int h, int w, double factor, int hkw, int crop) {
+  AdjointPlan a;
+  return adjoint_plan_of(B, h, w, factor, hkw, crop, false, &a) ? a.bytes : 0;
+}
+
+int sifsrt_degrade_bwd(const float* dout, const unsigned char* out_valid, float* dx, void* workspace, size_t workspace_bytes, int B,
+                       int h, int w, double factor, double mtf, int hkw, int crop, void* stream) {
+  if (!dout || !dx || !workspace || !aligned(workspace, 16) || !aligned(dout, 4) || !aligned(dx, 4)) return SIFSR_ERR_ARG;
+  AdjointPlan a;
+  if (!adjoint_plan_of(B, h, w, factor, hkw, crop, false, &a) || !(mtf > 0.0 && mtf < 1.0)) return SIFSR_ERR_SHAPE;
+  if (workspace_bytes < a.bytes) return SIFSR_ERR_WORKSPACE;
+  const AdjointBuffers b = buffers_of(workspace, a);
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = launch_table(a, b, psf_of(factor, mtf, a.hw), false, s);
+  return rc != SIFSR_OK ? rc : launch_adjoint(a, b, dout, out_valid, dx, B, h, w, s);
+}
+
+size_t sifsrt_lowpass_workspace_bytes(int B, int h, int w, double factor, int hkw) {
+  AdjointPlan a;
+  return adjoint_plan_of(B, h, w, factor, hkw, 0, true, &a) ? a.bytes : 0;
+}
+
+int sifsrt_lowpass_fwd(const float* x, float* out, void* workspace, size_t workspace_bytes, int B, int h, int w, double factor,
+                       double mtf, int hkw, void* stream) {
+  if (!x || !out || !workspace || !aligned(workspace, 16) || !aligned(x, 4) || !aligned(out, 4)) return SIFSR_ERR_ARG;
+  AdjointPlan a;
+  if (!adjoint_plan_of(B, h, w, factor, hkw, 0, true, &a) || !(mtf > 0.0 && mtf < 1.0)) return SIFSR_ERR_SHAPE;
+  if (workspace_bytes < a.bytes) return SIFSR_ERR_WORKSPACE;
+  const AdjointBuffers b = buffers_of(workspace, a);
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = launch_table(a, b, psf_of(factor, mtf, a.hw), true, s);
+  if (rc != SIFSR_OK) return rc;
+  const int gx = (w + BX - 1) / BX, gy = (h + BY - 1) / BY;
+  hipLaunchKernelGGL(degrade_rows_kernel, dim3(gx, gy, B), dim3(256), 0, s, x, (const unsigned char*)nullptr, b.wy, b.my, b.tmp,
+                     (unsigned char*)nullptr, h, w, h, a.K);
+  SIFSR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(degrade_cols_kernel, dim3(gx, gy, B), dim3(256), 0, s, b.tmp, (const unsigned char*)nullptr, b.wx, b.my, b.mx, out,
+                     (unsigned char*)nullptr, w, h, w, a.K, 0, 0.0f);
+  SIFSR_LAUNCH_CHECK();
+  return SIFSR_OK;
+}
+
+int sifsrt_lowpass_bwd(const float* dout, float* dx, void* workspace, size_t workspace_bytes, int B, int h, int w, double factor,
+                       double mtf, int hkw, void* stream) {
+  if (!dout || !dx || !workspace || !aligned(workspace, 16) || !aligned(dout, 4) || !aligned(dx, 4)) return SIFSR_ERR_ARG;
+  AdjointPlan a;
+  if (!adjoint_plan_of(B, h, w, factor, hkw, 0, true, &a) || !(mtf > 0.0 && mtf < 1.0)) return SIFSR_ERR_SHAPE;
+  if (workspace_bytes < a.bytes) return SIFSR_ERR_WORKSPACE;
+  const AdjointBuffers b = buffers_of(workspace, a);
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = launch_table(a, b, psf_of(factor, mtf, a.hw), true, s);
+  return rc != SIFSR_OK ? rc : launch_adjoint(a, b, dout, nullptr, dx, B, h, w, s);
 }
