@@ -37,6 +37,9 @@ Drop-in surface (SURVEY.md §8 b):
   sensor.downscale / lowpass / lr_shape / sif_loss / train_step  <- utils.py:1671-1706, :1833-1860 at any factor, as autograd ops
                                        (the adjoint of the banded sensor operator and the reflect-border MTF low-pass, forward
                                        and adjoint), the SIF loss and a training step at any ratio (include/sifsr_sensor.h)
+  ratio.upsample / geometry / prepare_tiles / granule_to_tiles / blend_tiles / predict_granule / predict_granule_gaps  <- no
+                                       counterpart: the bicubic resampler with an exact phase at any size, and whole-granule
+                                       prediction (seamless, gap-aware) at any ratio hr / window (include/sifsr_ratio.h)
   products.decode / PatchMiner / MinedPatches, dataset.MinedDataset  <- process_modis.py:38-335, data_preparation.py:32-102
                                        (raw granule arrays -> patches + statistics.json, on device)
 
@@ -47,7 +50,7 @@ and registers ``sifsr`` / ``sifsr.<submodule>`` as aliases of the same module ob
 import importlib
 import sys
 
-_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "degrade", "predict", "baselines", "products", "lpips", "adapt", "sensor")
+_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "degrade", "predict", "baselines", "products", "lpips", "adapt", "sensor", "ratio")
 for _m in _SUBMODULES:
     importlib.import_module(__name__ + "." + _m)
 

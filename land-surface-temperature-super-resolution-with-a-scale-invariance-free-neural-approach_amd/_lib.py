@@ -1,11 +1,11 @@
 """ctypes binding of libsifsr_hip.so.
 
 The signatures are parsed from the headers under ``include/`` -- the headers are the single source of truth for the C ABI.
-``FAMILIES`` and ``LATER_FAMILIES`` below are the two tables of them: ``include/sifsr_hip.h`` (``core``, prefix ``sifsr_``) and its
-extensions, one header and one symbol prefix each.  ``tests/test_capi_gate.py`` (rows of ``FAMILIES``) and
-``tests/test_sensor_host.py`` (rows of ``LATER_FAMILIES``) check, for every row, that the library exports exactly the declared
-symbols and that every writing entry point has memory-contract cases.  There is NO fallback: if the library is
-missing, of another ABI version, or a call fails, we raise.
+``FAMILIES``, ``LATER_FAMILIES`` and ``NEWER_FAMILIES`` below are the tables of them: ``include/sifsr_hip.h`` (``core``, prefix
+``sifsr_``) and its extensions, one header and one symbol prefix each.  ``tests/test_capi_gate.py`` (rows of ``FAMILIES``),
+``tests/test_sensor_host.py`` (rows of ``LATER_FAMILIES``) and ``tests/test_ratio_host.py`` (rows of ``NEWER_FAMILIES``) check, for
+every row, that the library exports exactly the declared symbols and that every writing entry point has memory-contract cases.
+There is NO fallback: if the library is missing, of another ABI version, or a call fails, we raise.
 """
 from __future__ import annotations
 
@@ -40,6 +40,11 @@ FAMILIES = {
 LATER_FAMILIES = {
     "sensor": ("sifsr_sensor.h", "sifsrt_"),
 }
+# Both tables above are pinned by their gates.  A family added from here on is ONE row below: lib(), header_path(), declared() and
+# writers() consult families(), and tests/test_ratio_host.py gates every row (its GPU module is tests/test_<family>_gpu.py).
+NEWER_FAMILIES = {
+    "ratio": ("sifsr_ratio.h", "sifsrr_"),
+}
 ABI_VERSION = 3
 # the entry points whose int return is a count, not a status: call() raises on a non-zero int from every other one
 COUNT_RETURNING = frozenset({
@@ -49,8 +54,13 @@ COUNT_RETURNING = frozenset({
 })
 
 
+def families() -> dict:
+    """family -> (header, prefix): the union of the three tables, in their order"""
+    return {**FAMILIES, **LATER_FAMILIES, **NEWER_FAMILIES}
+
+
 def header_path(family: str = "core") -> str:
-    return os.path.join(_ROOT, "include", (FAMILIES.get(family) or LATER_FAMILIES[family])[0])
+    return os.path.join(_ROOT, "include", families()[family][0])
 
 
 HEADER = header_path()
@@ -128,7 +138,7 @@ def lib():
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         decls = {}
-        for family in (*FAMILIES, *LATER_FAMILIES):
+        for family in families():
             decls.update(parse_header(header_path(family)))
         for name, (ret, args) in decls.items():
             fn = getattr(handle, name)     # AttributeError if the library lacks a declared symbol

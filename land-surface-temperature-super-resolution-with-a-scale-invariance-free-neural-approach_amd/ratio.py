@@ -1,0 +1,254 @@
+"""Whole-granule prediction at any ratio (include/sifsr_ratio.h, csrc/ratio.hip): what a model trained with
+``sensor.train_step(..., factor=3)`` -- or 2.5, or 2 -- needs to be used: a granule goes in at ratio ``hr / window`` and the
+super-resolved raster comes out, seamless and gap-aware.
+
+    upsample(x, size)       bicubic resampling to any larger size with an EXACT phase (the operator of ``F.interpolate(size=...,
+                            mode="bicubic", align_corners=False)``; torch rounds the scale and the source coordinate per pixel)
+    geometry(...)           the tile layout at ratio p / q = hr / window: (p, q, tiles, hr_shape), or SifsrError
+    prepare_tiles           the training-batch form: (T,1,w,w) and (T,1,P,P) -> (T,2,P,P)
+    granule_to_tiles / blend_tiles / predict_granule / predict_granule_gaps
+                            ``pipeline.granule_to_tiles`` / ``pipeline.blend_tiles`` / ``predict.predict_granule`` /
+                            ``gaps.predict_granule_gaps`` with the tile side ``hr`` as an argument
+
+A tile is ``window`` LST pixels and ``hr`` network pixels on a side.  The rules (``sifsrr_geometry``): 1 <= window <= 64; hr a
+multiple of 8 in 24..256 with window < hr <= 16 window; with p / q = hr / window in lowest terms, both sides of the LST raster and
+``overlap`` are multiples of q, 0 <= 2 overlap <= window, and the NDVI raster is exactly (h p / q, w p / q).  ``hr == 4 * window``
+is allowed and runs these kernels; the x4 functions of ``pipeline`` / ``predict`` / ``gaps`` keep theirs.  Everything is fp32 on the
+device; CPU tensors raise SifsrError: there is no CPU path.
+
+Out of scope here: ``conserve=`` at a ratio, a captured ``GranulePredictor`` at a ratio, ``adapt.adapt_granule``,
+``GraphedTrainStep`` and masks in the loss at a ratio, ratios that are not ``hr / window`` for such a pair (926.25 / 90 and
+231.656 / 90 stay with ``sifsr.degrade``), rerouting the drop-ins, and bf16."""
+from __future__ import annotations
+
+import ctypes
+from collections import namedtuple
+
+import torch
+
+from . import _lib, gaps
+from .pipeline import _UNIT
+
+Geometry = namedtuple("Geometry", "p q tiles hr_shape")
+MAX_LST_SIDE = 16384
+
+
+def geometry(lst_shape, window, hr, overlap=0, cover_edges=False):
+    """-> Geometry(p, q, (tiles_y, tiles_x), (H, W)) of an LST raster ``lst_shape`` cut into tiles of ``window`` LST pixels =
+    ``hr`` network pixels (``sifsrr_geometry``: host only); SifsrError for any violation of the rules in the module docstring."""
+    try:
+        h, w = (int(v) for v in lst_shape)
+        window, hr, overlap = int(window), int(hr), int(overlap)
+    except (TypeError, ValueError):
+        raise _lib.SifsrError(f"geometry: expected an (h, w) shape and integer window / hr / overlap, got {lst_shape!r}, {window!r}, "
+                              f"{hr!r}, {overlap!r}") from None
+    out6 = (ctypes.c_int * 6)()
+    rc = _lib.lib().sifsrr_geometry(h, w, window, hr, overlap, 1 if cover_edges else 0, out6)
+    if rc != 0:
+        raise _lib.SifsrError(
+            f"no tile layout for an LST raster {(h, w)} at window {window}, hr {hr}, overlap {overlap}: need 1 <= window <= 64, hr a "
+            f"multiple of 8 in 24..256 with window < hr <= 16 window, and with p / q = hr / window in lowest terms both raster sides "
+            f"(window..{MAX_LST_SIDE}) and the overlap multiples of q, 0 <= 2 overlap <= window (status {rc})")
+    p, q, ty, tx, H, W = out6
+    return Geometry(p, q, (ty, tx), (H, W))
+
+
+def _layout(lst_g, ndvi_shape, window, hr, overlap, cover_edges):
+    """validation shared by the granule entry points (before any launch) -> Geometry"""
+    if lst_g.dim() != 2:
+        raise _lib.SifsrError(f"lst granule: expected a 2-D raster, got {tuple(lst_g.shape)}")
+    g = geometry(lst_g.shape, window, hr, overlap, cover_edges)
+    if ndvi_shape is not None and tuple(ndvi_shape) != g.hr_shape:
+        raise _lib.SifsrError(f"ndvi granule must be {g.hr_shape} ({g.p}/{g.q} of the LST granule {tuple(lst_g.shape)}), got "
+                              f"{tuple(ndvi_shape)}")
+    return g
+
+
+def upsample(x, size):
+    """Bicubic resampling of x (h,w), (B,h,w) or (B,C,h,w) float32 on the device to ``size = (H, W)``, H >= h and W >= w, each axis
+    with its own ratio (``sifsrr_upsample``): A = -0.75, half-pixel centres, indices clamped to the raster -- the operator of
+    ``F.interpolate(x, size=(H, W), mode="bicubic", align_corners=False)`` with the phase of every output taken in integers, so an
+    axis with H == h is a bit-exact copy and the result is the float64 operator's to fp32 rounding at every ratio.
+
+    This is the ``lst_up`` of ``sensor.train_step``: ``ratio.upsample(lst, (H, W))``."""
+    if not isinstance(x, torch.Tensor):
+        raise _lib.SifsrError(f"upsample: expected a tensor, got {type(x).__name__}")
+    _lib.require_gpu(x, "x")
+    try:
+        H, W = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise _lib.SifsrError(f"upsample: size must be (H, W), got {size!r}") from None
+    if x.dim() not in (2, 3, 4):
+        raise _lib.SifsrError(f"upsample: expected (h,w), (B,h,w) or (B,C,h,w), got {tuple(x.shape)}")
+    h, w = x.shape[-2:]
+    B = x.numel() // max(1, h * w)
+    if B < 1 or h < 1 or w < 1 or H < h or W < w or h > MAX_LST_SIDE or w > MAX_LST_SIDE or H > 2 * MAX_LST_SIDE or W > 2 * MAX_LST_SIDE:
+        raise _lib.SifsrError(f"upsample: {tuple(x.shape)} -> {(H, W)}: needs a non-empty raster of sides <= {MAX_LST_SIDE} and a size "
+                              f"that is no smaller on either axis, at most {2 * MAX_LST_SIDE}")
+    out = torch.empty(tuple(x.shape[:-2]) + (H, W), dtype=torch.float32, device=x.device)
+    for b in range(0, B, 65535):                                        # (one launch holds 65535 images)
+        n = min(65535, B - b)
+        _lib.call("sifsrr_upsample", x.reshape(B, h, w)[b:b + n], out.view(B, H, W)[b:b + n], n, h, w, H, W, _lib.stream_ptr(x.device))
+    return out
+
+
+def prepare_tiles(lst, ndvi, stats=None, clip_ndvi=False):
+    """lst (T,1,w,w), ndvi (T,1,P,P) -> model input (T,2,P,P) = cat(upsample(z(lst), (P, P)), z(clip(ndvi))): the training-batch
+    form of ``granule_to_tiles``, as a column of T one-tile rasters (``sifsrr_tiles_prepare``; one device function with
+    ``upsample``).  ``stats=None``: inputs are already normalised."""
+    for t, n in ((lst, "lst"), (ndvi, "ndvi")):
+        if not isinstance(t, torch.Tensor):
+            raise _lib.SifsrError(f"prepare_tiles: {n} must be a tensor, got {type(t).__name__}")
+    _lib.require_gpu(lst, "lst"); _lib.require_gpu(ndvi, "ndvi")
+    if lst.dim() != 4 or ndvi.dim() != 4 or lst.shape[1] != 1 or lst.shape[2] != lst.shape[3] or ndvi.shape[2] != ndvi.shape[3] \
+            or tuple(ndvi.shape[:2]) != (lst.shape[0], 1) or lst.shape[0] < 1:
+        raise _lib.SifsrError(f"prepare_tiles expects lst (T,1,w,w) and ndvi (T,1,P,P); got {tuple(lst.shape)}, {tuple(ndvi.shape)}")
+    T, w, P = lst.shape[0], lst.shape[2], ndvi.shape[2]
+    geometry((w, w), w, P)
+    st = stats or _UNIT
+    x = torch.empty((T, 2, P, P), dtype=torch.float32, device=lst.device)
+    step = max(1, MAX_LST_SIDE // w)                                     # tiles per launch: a raster of (step w, w) LST pixels
+    for b in range(0, T, step):
+        n = min(step, T - b)
+        _lib.call("sifsrr_tiles_prepare", lst[b:b + n], ndvi[b:b + n], x[b:b + n], None, None, n, n * w, w, w, P, 0, 0,
+                  float(st["mean_lst"]), float(st["std_lst"]), float(st["mean_ndvi"]), float(st["std_ndvi"]), 1 if clip_ndvi else 0,
+                  _lib.stream_ptr(lst.device))
+    return x
+
+
+def _tile_buffer(out, n, planes, hr, device, what):
+    if out is None:
+        return torch.empty((n, planes, hr, hr), dtype=torch.float32, device=device)
+    _lib.require_gpu(out, what)
+    if out.dim() != 4 or out.shape[0] < n or tuple(out.shape[1:]) != (planes, hr, hr):
+        raise _lib.SifsrError(f"{what} must hold {(n, planes, hr, hr)}, got {tuple(out.shape)}")
+    return out[:n]
+
+
+def _stats4(stats):
+    return float(stats["mean_lst"]), float(stats["std_lst"]), float(stats["mean_ndvi"]), float(stats["std_ndvi"])
+
+
+def granule_to_tiles(lst_g, ndvi_g, stats, window, hr, clip_ndvi=True, overlap=0, cover_edges=False, out=None):
+    """Raw granule rasters lst_g (h,w) [K] and ndvi_g (h p/q, w p/q) -> (x (T,2,hr,hr), (tiles_y, tiles_x)): the tiles of
+    ``pipeline.tile_origins`` along each axis, each one z-scored, resampled to hr x hr clamped at the tile and concatenated with
+    its clipped, z-scored NDVI block -- what ``prepare_tiles`` gives for the same block.  ``out``: a buffer of at least T tiles to
+    write into; the first T tiles of it are returned."""
+    _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
+    g = _layout(lst_g, ndvi_g.shape, window, hr, overlap, cover_edges)
+    ty, tx = g.tiles
+    x = _tile_buffer(out, ty * tx, 2, hr, lst_g.device, "tile buffer")
+    h, w = lst_g.shape
+    _lib.call("sifsrr_tiles_prepare", lst_g, ndvi_g, x, None, None, ty * tx, h, w, window, hr, overlap, 1 if cover_edges else 0,
+              *_stats4(stats), 1 if clip_ndvi else 0, _lib.stream_ptr(lst_g.device))
+    return x, (ty, tx)
+
+
+def prepare_active_tiles(filled, ndvi_g, stats, active, n_active, cap, window, hr, overlap=0, cover_edges=False, clip_ndvi=True):
+    """-> x (cap,2,hr,hr): x[i] = the network input of tile active[i] for i < min(n_active, cap), the rest untouched; bit-identical
+    to that tile of ``granule_to_tiles(filled, ...)``.  ``active`` / ``n_active``: as ``gaps.select_tiles`` left them."""
+    _lib.require_gpu(filled, "filled granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
+    _layout(filled, ndvi_g.shape, window, hr, overlap, cover_edges)
+    if int(cap) < 1:
+        raise _lib.SifsrError(f"cap must be positive, got {cap}")
+    h, w = filled.shape
+    x = torch.empty((int(cap), 2, hr, hr), dtype=torch.float32, device=filled.device)
+    _lib.call("sifsrr_tiles_prepare", filled, ndvi_g, x, active, n_active, int(cap), h, w, window, hr, overlap, 1 if cover_edges else 0,
+              *_stats4(stats), 1 if clip_ndvi else 0, _lib.stream_ptr(filled.device))
+    return x
+
+
+def blend_tiles(sr, lst_shape, window, hr, stats, overlap=0, cover_edges=False, out=None):
+    """sr (T,1,hr,hr) normalised predictions of the tiles of ``granule_to_tiles`` -> the de-normalised raster (h p/q, w p/q) [K]:
+    the normalised feathered blend of ``pipeline.blend_tiles`` with tile side hr and HR overlap ``overlap p / q``
+    (``sifsrr_tiles_blend``), every pixel written, pixels no tile covers 0."""
+    _lib.require_gpu(sr, "sr")
+    g = geometry(lst_shape, window, hr, overlap, cover_edges)
+    ty, tx = g.tiles
+    if tuple(sr.shape) != (ty * tx, 1, hr, hr):
+        raise _lib.SifsrError(f"sr must be {(ty * tx, 1, hr, hr)} for this layout, got {tuple(sr.shape)}")
+    if out is None:
+        out = torch.empty(g.hr_shape, dtype=torch.float32, device=sr.device)
+    _lib.require_gpu(out, "output granule")
+    if tuple(out.shape) != g.hr_shape:
+        raise _lib.SifsrError(f"output granule must be {g.hr_shape}, got {tuple(out.shape)}")
+    h, w = (int(v) for v in lst_shape)
+    _lib.call("sifsrr_tiles_blend", sr, None, None, out, h, w, window, hr, overlap, 1 if cover_edges else 0, float(stats["mean_lst"]),
+              float(stats["std_lst"]), 0.0, _lib.stream_ptr(sr.device))
+    return out
+
+
+def blend_active_tiles(sr, slot, valid, window, hr, stats, overlap=0, cover_edges=False, fill_value=float("nan")):
+    """sr (>= n_active,1,hr,hr) normalised predictions in the order of ``active`` -> the de-normalised raster [K]: ``blend_tiles``
+    at the pixels of valid LST cells -- cell (Y q // p, X q // p) of output pixel (Y, X) --, ``fill_value`` at the others."""
+    _lib.require_gpu(sr, "sr")
+    if not isinstance(valid, torch.Tensor) or valid.dim() != 2:
+        raise _lib.SifsrError("valid must be a 2-D tensor")
+    g = geometry(valid.shape, window, hr, overlap, cover_edges)
+    valid = gaps._valid_raster(valid, valid.shape, sr.device)
+    ty, tx = g.tiles
+    if sr.dim() != 4 or sr.shape[0] < 1 or tuple(sr.shape[1:]) != (1, hr, hr):
+        raise _lib.SifsrError(f"sr must be (n_active, 1, {hr}, {hr}), got {tuple(sr.shape)}")
+    if not isinstance(slot, torch.Tensor) or slot.dtype != torch.int32 or tuple(slot.shape) != (ty * tx,) or slot.device != sr.device:
+        raise _lib.SifsrError(f"slot must be an int32 device tensor {(ty * tx,)}")
+    h, w = valid.shape
+    out = torch.empty(g.hr_shape, dtype=torch.float32, device=sr.device)
+    _lib.call("sifsrr_tiles_blend", sr, slot.contiguous(), valid, out, h, w, window, hr, overlap, 1 if cover_edges else 0,
+              float(stats["mean_lst"]), float(stats["std_lst"]), float(fill_value), _lib.stream_ptr(sr.device))
+    return out
+
+
+def _forwards(model, x, batch, hr):
+    sr = torch.empty((x.shape[0], 1, hr, hr), dtype=torch.float32, device=x.device)
+    for i in range(0, x.shape[0], batch):
+        sr[i:i + batch] = model(x[i:i + batch])
+    return sr
+
+
+@torch.inference_mode()
+def predict_granule(model, lst_g, ndvi_g, stats, window=64, hr=192, batch=256, overlap=0, cover_edges=False):
+    """``predict.predict_granule`` at ratio ``hr / window``: raw LST raster (h,w) [K] + raw NDVI raster (h p/q, w p/q) ->
+    super-resolved LST raster (h p/q, w p/q) [K].  Tiles are cut, normalised, resampled and concatenated by one kernel, pushed
+    through the network in eval mode in batches of ``batch``, then de-normalised and blended by another; ``overlap`` (LST pixels,
+    a multiple of q, 0..window/2) and ``cover_edges`` are those of ``predict.predict_granule``."""
+    _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
+    _layout(lst_g, ndvi_g.shape, window, hr, overlap, cover_edges)                            # (raises before any launch)
+    if int(batch) < 1:
+        raise _lib.SifsrError(f"batch must be positive, got {batch}")
+    model.eval()
+    x, _ = granule_to_tiles(lst_g, ndvi_g, stats, window, hr, True, overlap, cover_edges)
+    return blend_tiles(_forwards(model, x, int(batch), hr), lst_g.shape, window, hr, stats, overlap, cover_edges)
+
+
+@torch.inference_mode()
+def predict_granule_gaps(model, lst_g, ndvi_g, stats, mask=None, window=64, hr=192, batch=256, overlap=16, cover_edges=True,
+                         fill_value=float("nan"), return_info=False):
+    """``gaps.predict_granule_gaps`` at ratio ``hr / window``: raw LST raster (h,w) [K] with cloud / ocean / fill pixels as 0 K,
+    NaN or inf (and whatever ``mask`` rules out) + raw NDVI raster (h p/q, w p/q) -> the super-resolved raster, ``fill_value`` at
+    every output pixel (Y, X) whose LST cell (Y q // p, X q // p) is invalid.
+
+    ``gaps.fill_gaps`` and ``gaps.select_tiles`` run unchanged (they see only the LST raster; ``window`` must be a multiple of 4
+    for the selection, ``overlap`` a multiple of q); then the network input of the active tiles only, ceil(n_active / batch)
+    eval-mode forwards and the masked blend.  The read of the active count is the call's only host synchronisation.  At valid
+    pixels the result is bit-identical to ``predict_granule`` on the filled raster with the same layout; nothing valid: the
+    all-``fill_value`` raster, no forward.
+
+    ``return_info``: also {"valid": bool (h,w) device tensor, "n_active": int, "n_tiles": int}."""
+    _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
+    g = _layout(lst_g, ndvi_g.shape, window, hr, overlap, cover_edges)                        # (raises before any launch)
+    if int(window) % 4:
+        raise _lib.SifsrError(f"window must be a multiple of 4 for the tile selection, got {window}")
+    if int(batch) < 1:
+        raise _lib.SifsrError(f"batch must be positive, got {batch}")
+    model.eval()
+    filled, valid = gaps.fill_gaps(lst_g, mask)
+    slot, active, n_active = gaps.select_tiles(valid, window, overlap, cover_edges)
+    n = int(n_active.item())                                            # the one host sync
+    if n == 0:
+        out = torch.full(g.hr_shape, float(fill_value), dtype=torch.float32, device=lst_g.device)
+    else:
+        x = prepare_active_tiles(filled, ndvi_g, stats, active, n_active, n, window, hr, overlap, cover_edges)
+        out = blend_active_tiles(_forwards(model, x, int(batch), hr), slot, valid, window, hr, stats, overlap, cover_edges, fill_value)
+    if return_info:
+        return out, {"valid": valid.bool(), "n_active": n, "n_tiles": g.tiles[0] * g.tiles[1]}
+    return out
