@@ -40,6 +40,9 @@ Drop-in surface (SURVEY.md §8 b):
   ratio.upsample / geometry / prepare_tiles / granule_to_tiles / blend_tiles / predict_granule / predict_granule_gaps  <- no
                                        counterpart: the bicubic resampler with an exact phase at any size, and whole-granule
                                        prediction (seamless, gap-aware) at any ratio hr / window (include/sifsr_ratio.h)
+  rloss.valid_counts / sif_loss / sif_loss_with_grad / train_step / adapt_granule  <- no counterpart: the SIF loss at any ratio as
+                                       two fused kernels, masked (cloudy patches at x3, x2.5, x2), and fine-tuning on a granule at
+                                       any ratio hr / window (include/sifsr_rloss.h)
   products.decode / PatchMiner / MinedPatches, dataset.MinedDataset  <- process_modis.py:38-335, data_preparation.py:32-102
                                        (raw granule arrays -> patches + statistics.json, on device)
 
@@ -50,7 +53,7 @@ and registers ``sifsr`` / ``sifsr.<submodule>`` as aliases of the same module ob
 import importlib
 import sys
 
-_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "degrade", "predict", "baselines", "products", "lpips", "adapt", "sensor", "ratio")
+_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "degrade", "predict", "baselines", "products", "lpips", "adapt", "sensor", "ratio", "rloss")
 for _m in _SUBMODULES:
     importlib.import_module(__name__ + "." + _m)
 

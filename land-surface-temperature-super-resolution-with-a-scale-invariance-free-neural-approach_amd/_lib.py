@@ -1,9 +1,10 @@
 """ctypes binding of libsifsr_hip.so.
 
 The signatures are parsed from the headers under ``include/`` -- the headers are the single source of truth for the C ABI.
-``FAMILIES``, ``LATER_FAMILIES`` and ``NEWER_FAMILIES`` below are the tables of them: ``include/sifsr_hip.h`` (``core``, prefix
+``FAMILIES``, ``LATER_FAMILIES``, ``NEWER_FAMILIES`` and ``FAMILIES_4`` below are the tables of them: ``include/sifsr_hip.h`` (``core``, prefix
 ``sifsr_``) and its extensions, one header and one symbol prefix each.  ``tests/test_capi_gate.py`` (rows of ``FAMILIES``),
-``tests/test_sensor_host.py`` (rows of ``LATER_FAMILIES``) and ``tests/test_ratio_host.py`` (rows of ``NEWER_FAMILIES``) check, for
+``tests/test_sensor_host.py`` (rows of ``LATER_FAMILIES``), ``tests/test_ratio_host.py`` (rows of ``NEWER_FAMILIES``) and
+``tests/test_rloss_host.py`` (rows of ``FAMILIES_4``) check, for
 every row, that the library exports exactly the declared symbols and that every writing entry point has memory-contract cases.
 There is NO fallback: if the library is missing, of another ABI version, or a call fails, we raise.
 """
@@ -45,6 +46,12 @@ LATER_FAMILIES = {
 NEWER_FAMILIES = {
     "ratio": ("sifsr_ratio.h", "sifsrr_"),
 }
+# The three tables above and families() are pinned by their gates.  A family added after them is one row HERE: lib(), header_path(),
+# declared() and writers() consult all_families(); the gate of a row is tests/test_<family>_host.py (same checks, and the CONTRACT
+# table of tests/test_<family>_gpu.py).
+FAMILIES_4 = {
+    "rloss": ("sifsr_rloss.h", "sifsrq_"),
+}
 ABI_VERSION = 3
 # the entry points whose int return is a count, not a status: call() raises on a non-zero int from every other one
 COUNT_RETURNING = frozenset({
@@ -59,8 +66,13 @@ def families() -> dict:
     return {**FAMILIES, **LATER_FAMILIES, **NEWER_FAMILIES}
 
 
+def all_families() -> dict:
+    """family -> (header, prefix): every table, families() first and then FAMILIES_4 -- what the binding serves"""
+    return {**families(), **FAMILIES_4}
+
+
 def header_path(family: str = "core") -> str:
-    return os.path.join(_ROOT, "include", families()[family][0])
+    return os.path.join(_ROOT, "include", all_families()[family][0])
 
 
 HEADER = header_path()
@@ -138,7 +150,7 @@ def lib():
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         decls = {}
-        for family in families():
+        for family in all_families():
             decls.update(parse_header(header_path(family)))
         for name, (ret, args) in decls.items():
             fn = getattr(handle, name)     # AttributeError if the library lacks a declared symbol

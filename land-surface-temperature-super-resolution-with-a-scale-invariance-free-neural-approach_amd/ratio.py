@@ -16,9 +16,10 @@ multiple of 8 in 24..256 with window < hr <= 16 window; with p / q = hr / window
 is allowed and runs these kernels; the x4 functions of ``pipeline`` / ``predict`` / ``gaps`` keep theirs.  Everything is fp32 on the
 device; CPU tensors raise SifsrError: there is no CPU path.
 
-Out of scope here: ``conserve=`` at a ratio, a captured ``GranulePredictor`` at a ratio, ``adapt.adapt_granule``,
-``GraphedTrainStep`` and masks in the loss at a ratio, ratios that are not ``hr / window`` for such a pair (926.25 / 90 and
-231.656 / 90 stay with ``sifsr.degrade``), rerouting the drop-ins, and bf16."""
+Fine-tuning on a granule at a ratio and masks in the loss at a ratio are ``sifsr.rloss``.  Out of scope here:
+``conserve=`` at a ratio, a captured ``GranulePredictor`` at a ratio, ``GraphedTrainStep`` at a ratio, mining patches at a ratio,
+ratios that are not ``hr / window`` for such a pair (926.25 / 90 and 231.656 / 90 stay with ``sifsr.degrade``), rerouting the
+drop-ins, and bf16."""
 from __future__ import annotations
 
 import ctypes

@@ -1,0 +1,247 @@
+"""The scale-invariance-free loss at any ratio as two fused kernels, masked (include/sifsr_rloss.h,
+csrc/rloss.hip): what ``sensor.sif_loss`` composes from a few dozen launches, and what it cannot do -- leave out the cloudy cells of
+a partly valid patch -- in one call with its gradient.
+
+    valid_counts(valid, hr_shape)      (n1, n2) on the device: the valid LR cells and the HR pixels under them
+    sif_loss_with_grad / sif_loss      the loss block at ``factor``, optionally over the valid cells only
+    train_step                         ``sensor.train_step`` with the fused loss, ``valid=`` for cloudy patches
+    adapt_granule                      ``adapt.adapt_granule`` at ratio hr / window
+
+The LR cell of HR pixel (Y, X) is (Y h // H, X w // W): the rule under which ``ratio.predict_granule_gaps`` masks its output.
+Limits (``sifsrq_sif_loss``): 1 < factor <= 8, sides of ceil(factor) + 1 .. 16384, the half width of the sensor model at its
+default ceil(factor), at most 65535 images; ``sensor.sif_loss`` (composed, unmasked) serves what lies beyond them.  Everything is
+fp32 on the device; CPU tensors raise SifsrError: there is no CPU path.
+
+Out of scope here: ``GraphedTrainStep`` at a ratio (the call itself can be captured), ``conserve=`` at a ratio, a captured
+``GranulePredictor`` at a ratio, mining patches at a ratio, the ``hkw`` argument in the loss, and bf16."""
+from __future__ import annotations
+
+import torch
+
+from . import _lib, adapt, gaps, ratio, sensor
+from . import distributed as dp
+from .optim import FlatAdam
+
+MAX_FACTOR = 8.0
+MAX_SIDE = 16384
+_KINDS = {"sr2": 2, "sr1": 1}
+_LIMITS = (f"1 < factor <= {MAX_FACTOR:g}, sides of ceil(factor) + 1 .. {MAX_SIDE}, 1..65535 images; sensor.sif_loss serves what lies "
+           "beyond these limits")
+
+
+def _factor(factor, what):
+    try:
+        f = float(factor)
+    except (TypeError, ValueError):
+        raise _lib.SifsrError(f"{what}: factor must be a number, got {factor!r}") from None
+    if not 1.0 < f <= MAX_FACTOR:
+        raise _lib.SifsrError(f"{what}: factor {factor} is outside the limits of the fused loss ({_LIMITS})")
+    return f
+
+
+def _lr_mask(valid, shape, device, what):
+    if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.uint8, torch.bool):
+        raise _lib.SifsrError(f"{what}: valid must be a uint8 or bool tensor, got {getattr(valid, 'dtype', type(valid).__name__)}")
+    B, h, w = shape
+    if tuple(valid.shape) not in ((B, 1, h, w), (B, h, w)):
+        raise _lib.SifsrError(f"{what}: valid must be {(B, 1, h, w)} (one byte per LR cell), got {tuple(valid.shape)}")
+    if not valid.is_cuda or (device is not None and valid.device != device):
+        raise _lib.SifsrError(f"{what}: valid is on {valid.device}: this package only runs on a ROCm GPU (gfx950); there is no CPU path.")
+    return valid.contiguous().view(torch.uint8)
+
+
+def valid_counts(valid, hr_shape):
+    """valid (B,1,h,w) or (B,h,w) uint8 / bool on the device, ``hr_shape`` = (H, W) of the HR patch -> int64 (2,) on the device:
+    n1 = the valid LR cells, n2 = the HR pixels (Y, X) whose cell (Y h // H, X w // W) is valid (``sifsrq_valid_counts``; integer
+    arithmetic, nothing is read back).  At x2.5 a cell holds 2 or 3 pixels per axis: n2 is the exact count."""
+    if not isinstance(valid, torch.Tensor) or valid.dim() not in (3, 4):
+        raise _lib.SifsrError(f"valid_counts: valid must be a (B,1,h,w) or (B,h,w) tensor, got {getattr(valid, 'shape', type(valid).__name__)}")
+    try:
+        H, W = (int(v) for v in hr_shape)
+    except (TypeError, ValueError):
+        raise _lib.SifsrError(f"valid_counts: hr_shape must be (H, W), got {hr_shape!r}") from None
+    B, h, w = valid.shape[0], valid.shape[-2], valid.shape[-1]
+    v = _lr_mask(valid, (B, h, w), None, "valid_counts")
+    if not (1 <= B <= 65535 and 1 <= h <= H <= MAX_SIDE and 1 <= w <= W <= MAX_SIDE):
+        raise _lib.SifsrError(f"valid_counts: a mask {tuple(valid.shape)} under an HR patch {(H, W)}: needs 1..65535 images and LR sides "
+                              f"of 1 .. the HR side <= {MAX_SIDE}")
+    counts = torch.empty((2,), dtype=torch.int64, device=v.device)
+    _lib.call("sifsrq_valid_counts", v, B, h, w, H, W, counts, _lib.stream_ptr(v.device))
+    return counts
+
+
+def _args(kind, sr, lst, ndvi, factor, valid, counts, what, strict=False):
+    """every check that needs no launch -> (k, B, H, W, factor, valid or None, counts or None); ``strict``: valid and counts come
+    together or not at all (the C entry point's rule), otherwise missing counts are formed from valid"""
+    if kind not in _KINDS:
+        raise _lib.SifsrError(f"{what}: kind must be 'sr2' or 'sr1', got {kind!r}")
+    for t, n in ((sr, "sr"), (lst, "lst"), (ndvi, "ndvi")):
+        if not isinstance(t, torch.Tensor):
+            raise _lib.SifsrError(f"{what}: {n} must be a tensor, got {type(t).__name__}")
+    if sr.dim() != 4 or sr.shape[1] != 1 or ndvi.shape != sr.shape:
+        raise _lib.SifsrError(f"{what} expects sr and ndvi (B,1,H,W), got {tuple(sr.shape)} and {tuple(ndvi.shape)}")
+    f = _factor(factor, what)
+    B, _, H, W = sr.shape
+    if not (1 <= B <= 65535 and H <= MAX_SIDE and W <= MAX_SIDE):
+        raise _lib.SifsrError(f"{what}: {tuple(sr.shape)} is outside the limits of the fused loss ({_LIMITS})")
+    h, w = sensor.lr_shape(H, W, f)                                       # (raises SifsrError for sides under ceil(factor) + 1)
+    if tuple(lst.shape) != (B, 1, h, w):
+        raise _lib.SifsrError(f"{what}: lst must be {(B, 1, h, w)} at factor {factor} (sensor.lr_shape), got {tuple(lst.shape)}")
+    if (valid is None) != (counts is None) and (strict or valid is None):
+        raise _lib.SifsrError(f"{what}: exactly one of valid / counts was given: pass valid with counts = valid_counts(valid, (H, W)), "
+                              "or neither" + ("" if strict else " (counts=None with valid forms them)"))
+    for t, n in ((sr, "sr"), (lst, "lst"), (ndvi, "ndvi")):
+        _lib.require_gpu(t, n)
+    if valid is not None:
+        valid = _lr_mask(valid, (B, h, w), sr.device, what)
+        if counts is None:
+            counts = valid_counts(valid, (H, W))
+        if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or tuple(counts.shape) != (2,) or counts.device != sr.device \
+                or not counts.is_contiguous():
+            raise _lib.SifsrError(f"{what}: counts must be the int64 (2,) device tensor of valid_counts(valid, (H, W))")
+    return _KINDS[kind], B, H, W, f, valid, counts
+
+
+def _call(k, sr, lst, ndvi, B, H, W, f, mean, std, alpha, gamma, valid, counts, with_grad):
+    need = _lib.call("sifsrq_sif_loss_workspace_bytes", k, B, H, W, f)
+    if need == 0:
+        raise _lib.SifsrError(f"sif_loss: {(B, 1, H, W)} at factor {f} is outside the limits of the fused loss ({_LIMITS})")
+    ws = torch.empty((need,), dtype=torch.uint8, device=sr.device)
+    losses = torch.empty((3,), dtype=torch.float32, device=sr.device)
+    dsr = torch.empty_like(sr) if with_grad else None
+    _lib.call("sifsrq_sif_loss", k, sr, lst, valid, counts, ndvi, B, H, W, f, float(mean), float(std), float(alpha), float(gamma), ws, need,
+              losses, dsr, _lib.stream_ptr(sr.device))
+    return losses, dsr
+
+
+def sif_loss_with_grad(kind, sr, lst, ndvi, factor, mean, std, alpha, gamma, valid=None, counts=None):
+    """The loss block of ``sensor.sif_loss`` and d loss / d sr WITHOUT an autograd node, fused (``sifsrq_sif_loss``):
+
+        ds   = mean over the valid LR cells of      huber((downscale(sr std + mean, factor, mtf 0.1) - mean) / std - lst)
+        pl   = mean over the HR pixels under them of huber((sr - lowpass(sr, factor, 0.25)) - gamma (ndvi - lowpass(ndvi, ..)))  'sr2'
+                                                     huber(sobel_bank(sr) - gamma sobel_bank(ndvi))                              'sr1'
+        loss = alpha ds + (1 - alpha) pl
+
+    sr, ndvi (B,1,H,W), lst (B,1,*sensor.lr_shape(H, W, factor)); ``valid`` (B,1,h,w) uint8 / bool marks the LR cells that count,
+    ``counts`` = ``valid_counts(valid, (H, W))``; both or neither (exactly one raises SifsrError): without them every cell counts,
+    bit for bit what an all-ones mask gives.  ``lst`` under an invalid cell is never read, and the gradient there is what the blur and the low-pass of the valid
+    neighbours leave.  -> (losses (3,) = (ds, pl, loss), dsr (B,1,H,W)), device tensors; nothing is read back.  ``sr`` may carry a
+    graph; it is only read."""
+    srd = sr.detach().contiguous() if isinstance(sr, torch.Tensor) else sr
+    lst, ndvi = (t.contiguous() if isinstance(t, torch.Tensor) else t for t in (lst, ndvi))
+    k, B, H, W, f, valid, counts = _args(kind, srd, lst, ndvi, factor, valid, counts, "sif_loss_with_grad", strict=True)
+    return _call(k, srd, lst, ndvi, B, H, W, f, mean, std, alpha, gamma, valid, counts, True)
+
+
+class _RatioSifLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sr, lst, ndvi, valid, counts, k, B, H, W, f, mean, std, alpha, gamma):
+        losses, dsr = _call(k, sr, lst, ndvi, B, H, W, f, mean, std, alpha, gamma, valid, counts, ctx.needs_input_grad[0])
+        ctx.dsr = dsr
+        ds, pl, loss = losses[0], losses[1], losses[2]
+        ctx.mark_non_differentiable(ds, pl)
+        ctx.set_materialize_grads(False)
+        return ds, pl, loss
+
+    @staticmethod
+    def backward(ctx, g_ds, g_pl, g_loss):
+        dsr = ctx.dsr
+        ctx.dsr = None
+        if g_loss is None:
+            return (None,) * 14
+        if dsr is None:
+            raise _lib.SifsrError("sif_loss: backward called twice (d loss / d sr was released after the first call)")
+        return (dsr * g_loss,) + (None,) * 13
+
+
+def sif_loss(kind, sr, lst, ndvi, factor, mean, std, alpha, gamma, valid=None, counts=None):
+    """``sif_loss_with_grad`` as an autograd op: -> (ds, pl, loss) as 0-d device tensors; only ``loss`` carries a gradient (to
+    ``sr``), the stored d loss / d sr scaled by the incoming one.  With ``valid`` given and ``counts=None`` the counts are formed
+    by ``valid_counts``."""
+    srd = sr.contiguous() if isinstance(sr, torch.Tensor) else sr
+    lst, ndvi = (t.contiguous() if isinstance(t, torch.Tensor) else t for t in (lst, ndvi))
+    k, B, H, W, f, valid, counts = _args(kind, srd.detach() if isinstance(srd, torch.Tensor) else srd, lst, ndvi, factor, valid, counts,
+                                         "sif_loss")
+    return _RatioSifLoss.apply(srd, lst, ndvi, valid, counts, k, B, H, W, f, mean, std, alpha, gamma)
+
+
+def train_step(model, optimizer, lst, lst_up, ndvi, stats, alpha, gamma, factor, kind="sr2", valid=None, counts=None, sync_grads=True,
+               return_sr=False):
+    """``sensor.train_step`` with the fused loss: ``sr = model(cat(lst_up, ndvi))``, the loss and d loss / d sr of
+    ``sif_loss_with_grad(..., factor, valid=, counts=)`` (``counts=None`` with ``valid``: formed by ``valid_counts``),
+    ``sr.backward(dsr)``, ``optimizer.step()``.  With ``valid`` (B,1,h,w) the step trains on partly cloudy patches:
+    ``lst`` / ``lst_up`` are then the FILLED patch and its upsampling, and an invalid cell adds nothing to the loss or the gradient.
+    Works with ``model.bn_frozen``.  Under data parallelism each rank normalises by its own counts before the gradients are
+    averaged, as ``train.train_step`` does.  Returns device scalars (ds_loss, percep_loss, loss) -- no host sync -- and, with
+    ``return_sr``, the detached training-mode prediction."""
+    model.train()
+    optimizer.zero_grad(set_to_none=True)
+    sr = model(torch.cat((lst_up, ndvi), dim=1))
+    srd, lst, ndvi = sr.detach().contiguous(), lst.contiguous(), ndvi.contiguous()
+    k, B, H, W, f, valid, counts = _args(kind, srd, lst, ndvi, factor, valid, counts, "train_step")
+    losses, dsr = _call(k, srd, lst, ndvi, B, H, W, f, stats["mean_lst"], stats["std_lst"], alpha, gamma, valid, counts, True)
+    sr.backward(dsr)
+    if sync_grads:
+        dp.allreduce_gradients(model, optimizer)
+    optimizer.step()
+    if return_sr:
+        return losses[0], losses[1], losses[2], sr.detach()
+    return losses[0], losses[1], losses[2]
+
+
+def adapt_granule(model, lst_g, ndvi_g, stats, window, hr, mask=None, steps=20, lr=1e-5, alpha=0.5, gamma=1.0, kind="sr2", batch=16,
+                  overlap=0, cover_edges=False, optimizer=None):
+    """``adapt.adapt_granule`` at ratio ``hr / window``: ``steps`` optimisation steps of the masked loss on the active tiles of one
+    gappy granule (raw LST (h,w) [K], raw NDVI (h p/q, w p/q), ``mask`` as in ``gaps.fill_gaps``), BatchNorm statistics frozen.
+    The layout is ``ratio.geometry``'s; fill, selection and loss targets are ``gaps.fill_gaps``, ``gaps.select_tiles`` and
+    ``adapt.tile_targets`` (they see the LST raster only), the network inputs ``ratio.prepare_active_tiles``; step i is
+    ``rloss.train_step(..., factor=hr / window, valid=)`` on the min(batch, n_active) tiles from position i * batch of the active
+    list, cyclic.  A ``(window, hr)`` whose ``sensor.lr_shape(hr, hr, hr / window)`` is not ``(window, window)`` -- (16, 20): the
+    sensor model's crop leaves 17 -- is refused before any launch.  The read of the active count is the only host synchronisation;
+    no active tile: no step, no forward.  Returns an ``adapt.Adaptation``; the model's mode and ``bn_frozen`` are as they were."""
+    for t, n in ((lst_g, "lst granule"), (ndvi_g, "ndvi granule")):
+        if not isinstance(t, torch.Tensor):
+            raise _lib.SifsrError(f"adapt_granule: {n} must be a tensor, got {type(t).__name__}")
+    if lst_g.dim() != 2:
+        raise _lib.SifsrError(f"lst granule: expected a 2-D raster, got {tuple(lst_g.shape)}")
+    try:
+        window, hr = int(window), int(hr)
+    except (TypeError, ValueError):
+        raise _lib.SifsrError(f"adapt_granule: window and hr must be integers, got {window!r}, {hr!r}") from None
+    if window < 1 or hr <= window:
+        raise _lib.SifsrError(f"adapt_granule: needs 1 <= window < hr, got window {window}, hr {hr}")
+    factor = _factor(hr / window, "adapt_granule")
+    if kind not in _KINDS:
+        raise _lib.SifsrError(f"adapt_granule: kind must be 'sr2' or 'sr1', got {kind!r}")
+    got = sensor.lr_shape(hr, hr, factor)
+    if got != (window, window):
+        raise _lib.SifsrError(f"adapt_granule: at ratio {hr}/{window} the sensor model sees {got} of an {(hr, hr)} tile, not "
+                              f"{(window, window)} (sensor.lr_shape: the crop of the sensor model cuts floor(ceil(factor) / factor) cells on "
+                              "each side); choose a window and hr whose LR tile is the window")
+    ratio._layout(lst_g, ndvi_g.shape, window, hr, overlap, cover_edges)                       # (raises before any launch)
+    if window % 4:
+        raise _lib.SifsrError(f"window must be a multiple of 4 for the tile selection, got {window}")
+    if int(batch) < 1 or int(steps) < 0:
+        raise _lib.SifsrError(f"batch must be positive and steps non-negative, got {batch}, {steps}")
+    _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
+    steps, batch = int(steps), int(batch)
+    filled, valid = gaps.fill_gaps(lst_g, mask)
+    _, active, n_active = gaps.select_tiles(valid, window, overlap, cover_edges)
+    n = int(n_active.item())                                            # the one host sync
+    losses = torch.zeros((steps, 3), dtype=torch.float32, device=lst_g.device)
+    if n == 0 or steps == 0:
+        return adapt.Adaptation(model, None, losses[:0] if n == 0 else losses, n, optimizer)
+    start = model.flat_parameters().detach().clone()
+    x = ratio.prepare_active_tiles(filled, ndvi_g, stats, active, n_active, n, window, hr, overlap, cover_edges)
+    if optimizer is None:
+        optimizer = FlatAdam(model.parameters(), lr=lr)
+    b = min(batch, n)
+    with adapt.frozen_bn(model):
+        for i in range(steps):
+            first = (i * batch) % n
+            idx = (torch.arange(first, first + b, device=x.device) % n) if first + b > n else slice(first, first + b)
+            xb = x[idx]
+            lst, vt, _ = adapt.tile_targets(filled, valid, active, n_active, first, b, stats, window, overlap, cover_edges)
+            out = train_step(model, optimizer, lst, xb[:, 0:1], xb[:, 1:2], stats, alpha, gamma, factor, kind=kind, valid=vt)
+            losses[i, 0] = out[0]; losses[i, 1] = out[1]; losses[i, 2] = out[2]
+    return adapt.Adaptation(model, start, losses, n, optimizer)

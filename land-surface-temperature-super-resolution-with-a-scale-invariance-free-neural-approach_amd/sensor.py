@@ -11,9 +11,10 @@ scale-invariance-free loss needs when the ratio between the two sensors is not 4
 
 Everything is fp32 on the device, accumulated in float64 and rounded once; CPU tensors raise SifsrError: there is no CPU path.
 
-Out of scope here: masks in the loss (``valid`` is an argument of ``downscale`` alone), a fused loss kernel at a ratio (the loss is
-composed from autograd ops; at x4 ``sif_ops.sif_loss`` stays the fused path), ``GraphedTrainStep`` / ``adapt.adapt_granule`` at a
-ratio, and the drop-in's ``factor != 4`` calls, which keep their refusal."""
+The loss here is composed from autograd ops and has no mask (``valid`` is an argument of ``downscale`` alone); the fused, masked
+loss at a ratio, its training step and ``adapt_granule`` at a ratio are ``sifsr.rloss``; at x4
+``sif_ops.sif_loss`` stays the fused path.  Out of scope: ``GraphedTrainStep`` at a ratio, the ``hkw`` argument in the loss, and the
+drop-in's ``factor != 4`` calls, which keep their refusal."""
 from __future__ import annotations
 
 import torch
