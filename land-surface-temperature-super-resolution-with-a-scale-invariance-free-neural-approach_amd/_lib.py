@@ -1,11 +1,9 @@
 """ctypes binding of libsifsr_hip.so.
 
 The signatures are parsed from the headers under ``include/`` -- the headers are the single source of truth for the C ABI.
-``FAMILIES``, ``LATER_FAMILIES``, ``NEWER_FAMILIES`` and ``FAMILIES_4`` below are the tables of them: ``include/sifsr_hip.h`` (``core``, prefix
-``sifsr_``) and its extensions, one header and one symbol prefix each.  ``tests/test_capi_gate.py`` (rows of ``FAMILIES``),
-``tests/test_sensor_host.py`` (rows of ``LATER_FAMILIES``), ``tests/test_ratio_host.py`` (rows of ``NEWER_FAMILIES``) and
-``tests/test_rloss_host.py`` (rows of ``FAMILIES_4``) check, for
-every row, that the library exports exactly the declared symbols and that every writing entry point has memory-contract cases.
+``FAMILIES`` below is the one table of them: ``include/sifsr_hip.h`` (``core``, prefix ``sifsr_``) and its extensions, one header
+and one symbol prefix each.  ``tests/test_capi_gate.py`` checks, for every row, that the library exports exactly the declared
+symbols and that every writing entry point has memory-contract cases.
 There is NO fallback: if the library is missing, of another ABI version, or a call fails, we raise.
 """
 from __future__ import annotations
@@ -18,8 +16,10 @@ import torch  # noqa: F401  (must be imported first: the library binds to the li
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
-# The C ABI: family -> (header under include/, symbol prefix).  `core` is the main header; every other row is an extension with
-# the same declaration style.  lib() binds them all; tests/test_capi_gate.py gates each row against the built library.
+# The C ABI: family -> (header under include/, symbol prefix).  A family is ONE row: `core` is the main header, every other row an
+# extension in the same declaration style whose memory-contract cases are the CONTRACT of tests/test_<family>_gpu.py.  lib() binds
+# every row; tests/test_capi_gate.py gates every row against the built library and the include/ directory, so a new family adds a
+# header, a row and that GPU module, and no gate of its own.
 FAMILIES = {
     "core": ("sifsr_hip.h", "sifsr_"),
     "mosaic": ("sifsr_mosaic.h", "sifsrx_"),
@@ -34,22 +34,8 @@ FAMILIES = {
     "spectra": ("sifsr_spectra.h", "sifsrf_"),
     "degrade": ("sifsr_degrade.h", "sifsrs_"),
     "adapt": ("sifsr_adapt.h", "sifsra_"),
-}
-# Header families added after tests/test_capi_gate.py pinned the rows above: same declaration style, bound by lib() and served by
-# header_path() / declared() / writers() like them.  The gate for these rows is tests/test_sensor_host.py (the same checks, and the
-# CONTRACT table of tests/test_sensor_gpu.py); a later refactor that may edit the gate merges the two tables.
-LATER_FAMILIES = {
     "sensor": ("sifsr_sensor.h", "sifsrt_"),
-}
-# Both tables above are pinned by their gates.  A family added from here on is ONE row below: lib(), header_path(), declared() and
-# writers() consult families(), and tests/test_ratio_host.py gates every row (its GPU module is tests/test_<family>_gpu.py).
-NEWER_FAMILIES = {
     "ratio": ("sifsr_ratio.h", "sifsrr_"),
-}
-# The three tables above and families() are pinned by their gates.  A family added after them is one row HERE: lib(), header_path(),
-# declared() and writers() consult all_families(); the gate of a row is tests/test_<family>_host.py (same checks, and the CONTRACT
-# table of tests/test_<family>_gpu.py).
-FAMILIES_4 = {
     "rloss": ("sifsr_rloss.h", "sifsrq_"),
 }
 ABI_VERSION = 3
@@ -61,18 +47,8 @@ COUNT_RETURNING = frozenset({
 })
 
 
-def families() -> dict:
-    """family -> (header, prefix): the union of the three tables, in their order"""
-    return {**FAMILIES, **LATER_FAMILIES, **NEWER_FAMILIES}
-
-
-def all_families() -> dict:
-    """family -> (header, prefix): every table, families() first and then FAMILIES_4 -- what the binding serves"""
-    return {**families(), **FAMILIES_4}
-
-
 def header_path(family: str = "core") -> str:
-    return os.path.join(_ROOT, "include", all_families()[family][0])
+    return os.path.join(_ROOT, "include", FAMILIES[family][0])
 
 
 HEADER = header_path()
@@ -150,7 +126,7 @@ def lib():
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         decls = {}
-        for family in all_families():
+        for family in FAMILIES:
             decls.update(parse_header(header_path(family)))
         for name, (ret, args) in decls.items():
             fn = getattr(handle, name)     # AttributeError if the library lacks a declared symbol

@@ -2,21 +2,9 @@
 host-only introspection entry points agree with the oracle's view of the reference layout.
 No compute call is made (there is no GPU here)."""
 import ctypes
-import os
-
-import pytest
 
 from oracle import sif_oracle as O
-
-
-@pytest.fixture(scope="module")
-def L():
-    import sifsr  # noqa: F401
-    from sifsr import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib
+from tests.capi_host import L, exported  # noqa: F401  (L is the fixture)
 
 
 def test_every_declared_symbol_is_exported(L):
@@ -26,10 +14,8 @@ def test_every_declared_symbol_is_exported(L):
     missing = [n for n in names if not hasattr(handle, n)]
     assert not missing, missing
     # and nothing undeclared leaks out with our prefix
-    import subprocess
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and "sifsr_" in ln}
-    assert exported == set(names), exported ^ set(names)
+    under = {n for n in exported(L.LIB_PATH) if "sifsr_" in n}
+    assert under == set(names), under ^ set(names)
 
 
 def test_header_parser_types(L):

@@ -3,14 +3,14 @@
   * the restatement tests/ratio_reference.py: its integer-phase resampler IS torch's float64 bicubic ``F.interpolate`` (to 1e-12),
   * ``sifsrr_geometry`` (host only) against the restatement over a sweep that holds every rule's first violation; the tile origins
     are ``sifsrx_tile_origin``'s, mapped to whole HR pixels, and at hr = 4 win the counts are ``sifsrx_tile_count``'s,
-  * the gate of the third header table, ``sifsr._lib.NEWER_FAMILIES``: for EVERY row the checks tests/test_sensor_host.py applies to
-    its row; the GPU module of a family is tests/test_<family>_gpu.py by convention, so a later family adds a row and no gate,
+  * the pins of include/sifsr_ratio.h for the ``sifsrr_`` entry points (the gate itself is tests/test_capi_gate.py, which also holds
+    the exemption of ``sifsrr_geometry``): the row, the declared names, the writers, and what the memory-contract cases of
+    tests/test_ratio_gpu.py cover,
   * the public names of ``sifsr.ratio`` and the refusals that need no GPU."""
 import ctypes
 import importlib
 import inspect
 import math
-import os
 
 import numpy as np
 import pytest
@@ -18,9 +18,8 @@ import torch
 import torch.nn.functional as F
 
 from tests import ratio_reference as R
-from tests.capi_host import L, exported  # noqa: F401  (L is the fixture)
+from tests.capi_host import L  # noqa: F401  (the fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPE_ERR, ARG_ERR = 1001, 1002
 # (h, w) -> (H, W): the network's ratios at the tile sizes of the GPU tests and of training, a non-integer one per axis, a 1-pixel
 # raster (every index clamps) and a mixed case with a ratio of its own per axis
@@ -130,77 +129,32 @@ def test_origins_are_the_mosaic_s_and_whole_hr_pixels(L):
         assert hr_shape == (4 * h, 4 * w)
 
 
-# ---- 3. the gate of the third header table --------------------------------------------------------------------------------------
-# Entry points that take a non-const pointer but write no device memory, per family
-EXEMPT = {"ratio": {"sifsrr_geometry": "host only: six ints on the host"}}
-# the pins that are this family's alone
-NAMES = {"ratio": ["sifsrr_geometry", "sifsrr_tiles_blend", "sifsrr_tiles_prepare", "sifsrr_upsample"]}
-WRITERS = {"ratio": {"sifsrr_geometry": ["out6"], "sifsrr_upsample": ["out"], "sifsrr_tiles_prepare": ["x"], "sifsrr_tiles_blend": ["out"]}}
+# ---- 3. the pins of include/sifsr_ratio.h (the gate itself is tests/test_capi_gate.py) -------------------------------------------
+NAMES = ["sifsrr_geometry", "sifsrr_tiles_blend", "sifsrr_tiles_prepare", "sifsrr_upsample"]
+WRITERS = {"sifsrr_geometry": ["out6"], "sifsrr_upsample": ["out"], "sifsrr_tiles_prepare": ["x"], "sifsrr_tiles_blend": ["out"]}
 
 
-def newer(L):
-    return list(L.NEWER_FAMILIES)
-
-
-def test_the_third_table(L):
-    assert L.NEWER_FAMILIES["ratio"] == ("sifsr_ratio.h", "sifsrr_") and list(L.NEWER_FAMILIES)[0] == "ratio"
-    assert len(L.FAMILIES) == 13 and list(L.LATER_FAMILIES) == ["sensor"]            # pinned by their own gates
-    union = L.families()
-    assert list(union) == [*L.FAMILIES, *L.LATER_FAMILIES, *L.NEWER_FAMILIES] and len(union) == 14 + len(L.NEWER_FAMILIES)
-    assert len({p for _, p in union.values()}) == len(union) == len({h for h, _ in union.values()})
-    for family, (header, prefix) in L.NEWER_FAMILIES.items():
-        assert header == f"sifsr_{family}.h" and prefix.startswith("sifsr") and prefix.endswith("_") and prefix != "sifsr_"
-        assert os.path.samefile(L.header_path(family), os.path.join(ROOT, "include", header))
-        assert os.path.exists(os.path.join(ROOT, "tests", f"test_{family}_gpu.py"))
-        assert L.declared(family) == NAMES[family]
-    assert L.call("sifsr_abi_version") == L.ABI_VERSION == 3
-
-
-def test_exported_symbols_are_the_declared_ones(L):
-    union = L.families()
-    for family in newer(L):
-        prefix = union[family][1]
-        names = L.declared(family)
-        assert names and not [n for n in names if not n.startswith(prefix)]
-        assert not [n for n in names if "sifsr_" in n]                       # outside the core header's export check
-        for other, (_, op) in union.items():
-            if other == family:
-                continue
-            assert not prefix.startswith(op) and not op.startswith(prefix), other
-            assert not set(names) & set(L.declared(other)), other
-            assert not [n for n in names if n.startswith(op)], other
-            assert not [n for n in L.declared(other) if n.startswith(prefix)], other
-        under = {n for n in exported(L.LIB_PATH) if n.startswith(prefix)}
-        assert under == set(names), f"exported but not declared, or declared but not exported: {sorted(under ^ set(names))}"
-        handle = ctypes.CDLL(L.LIB_PATH)
-        assert not [n for n in names if not hasattr(handle, n)]
-        assert not [n for n in names if not hasattr(L.lib(), n)]            # the binding carries the family
-        for n in names:
-            fn = getattr(L.lib(), n)
-            assert fn.restype is ctypes.c_int and fn.argtypes, n
-        assert not set(names) & L.COUNT_RETURNING
-    assert len(L.COUNT_RETURNING) == 14
+def test_the_row_and_the_declared_names(L):
+    assert L.FAMILIES["ratio"] == ("sifsr_ratio.h", "sifsrr_")
+    assert L.declared("ratio") == NAMES
+    decls = L.parse_header(L.header_path("ratio"))
+    assert all(decls[n][0] is ctypes.c_int for n in NAMES)                  # every one returns a status; none a size
+    assert not set(NAMES) & L.COUNT_RETURNING and len(L.COUNT_RETURNING) == 14
 
 
 def test_every_writing_entry_point_has_contract_cases(L):
-    for family in newer(L):
-        T = importlib.import_module(f"tests.test_{family}_gpu")
-        writers, exempt, covered = L.writers(family), EXEMPT.get(family, {}), set(T.CONTRACT)
-        assert writers == WRITERS[family] and "stream" not in sum(writers.values(), [])
-        for name in exempt:
-            assert name in writers and name not in covered, name          # the exemption list stays minimal and current
-        assert covered == set(writers) - set(exempt), f"CONTRACT of tests/test_{family}_gpu.py and the writers differ: {sorted(covered ^ set(writers))}"
-        assert set(L.declared(family)) - set(writers) == set()             # every entry point of the family takes a pointer it may write
-        for name, cases in T.CONTRACT.items():
-            assert len(cases) >= 3, name
-    assert list(EXEMPT["ratio"]) == ["sifsrr_geometry"]
+    T = importlib.import_module("tests.test_ratio_gpu")
+    writers = L.writers("ratio")
+    assert writers == WRITERS
+    assert set(L.declared("ratio")) - set(writers) == set()                 # every entry point of the family takes a pointer it may write
+    for name, cases in T.CONTRACT.items():
+        assert len(cases) >= 3, name
     # the const inputs are declared const: run_contract's arena checks them untouched
     decls = L.parse_header(L.header_path("ratio"))
-    consts = {n: [a[0] for a in decls[n][1] if a.pointer and a.const] for n in WRITERS["ratio"]}
+    consts = {n: [a[0] for a in decls[n][1] if a.pointer and a.const] for n in WRITERS}
     assert consts == {"sifsrr_geometry": [], "sifsrr_upsample": ["x"], "sifsrr_tiles_prepare": ["lst", "ndvi", "active", "n_active"],
                       "sifsrr_tiles_blend": ["sr", "slot", "valid"]}
     # what the cases hold
-    T = importlib.import_module("tests.test_ratio_gpu")
     assert {(1, 1, 1, 8, 8), (1, 2, 3, 7, 5)} <= set(T.UPSAMPLE_CONTRACT) and any(c[0] > 1 for c in T.UPSAMPLE_CONTRACT)
     assert {c[:2] for c in T.PREPARE_CONTRACT} >= {(8, 24), (16, 40), (12, 32)}
     modes = {c[6] for c in T.PREPARE_CONTRACT}

@@ -3,8 +3,8 @@
   * the restatement tests/rloss_reference.py: with an all-ones mask it is the unmasked composition of the operators of
     tests/sensor_reference.py; at factor 4 it is compared with the oracle's /4 masked loss (tests/masked_reference.py);
   * the cell rule P and the count n2; the LDS condition of pass A (the windows of one LR tile span at most RL_CAP pixels);
-  * the gate of the `sifsrq_` entry points of include/sifsr_rloss.h, the one row of sifsr._lib.FAMILIES_4, with the checks
-    tests/test_sensor_host.py applies to its row;
+  * the pins of include/sifsr_rloss.h for the `sifsrq_` entry points (the gate itself is tests/test_capi_gate.py): the row, the
+    declared names, the writers, which entry point is host only, and what the memory-contract cases of tests/test_rloss_gpu.py cover;
   * the public names of sifsr.rloss and the refusals that need no GPU;
   * both Huber branches are reached by the inputs of tests/test_rloss_gpu.py."""
 import ctypes
@@ -22,7 +22,7 @@ from tests import degrade_reference as R
 from tests import masked_reference as MR
 from tests import rloss_reference as Q
 from tests import sensor_reference as SR
-from tests.capi_host import L, exported  # noqa: F401  (L is the fixture)
+from tests.capi_host import L  # noqa: F401  (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCE = open(os.path.join(ROOT, "land-surface-temperature-super-resolution-with-a-scale-invariance-free-neural-approach_amd", "csrc",
@@ -141,51 +141,25 @@ def test_the_windows_of_an_lr_tile_fit_the_staged_region():
     assert 60 <= worst <= CAP
 
 
-# ---- 3. the gate of the fourth header table -------------------------------------------------------------------------------------
-FAMILY, PREFIX = "rloss", "sifsrq_"
+# ---- 3. the pins of include/sifsr_rloss.h (the gate itself is tests/test_capi_gate.py) -------------------------------------------
 NAMES = ["sifsrq_sif_loss", "sifsrq_sif_loss_workspace_bytes", "sifsrq_valid_counts"]
 WRITERS = {"sifsrq_valid_counts": ["counts2"], "sifsrq_sif_loss": ["workspace", "losses3", "dsr"]}
 HOST_ONLY = {"sifsrq_sif_loss_workspace_bytes"}
 
 
-def test_the_fourth_table(L):
-    assert L.FAMILIES_4 == {FAMILY: ("sifsr_rloss.h", PREFIX)}
-    # the three older tables, families() and the ABI version are as their own gates pin them
-    assert len(L.FAMILIES) == 13 and L.LATER_FAMILIES == {"sensor": ("sifsr_sensor.h", "sifsrt_")}
-    assert L.NEWER_FAMILIES == {"ratio": ("sifsr_ratio.h", "sifsrr_")}
-    assert L.families() == {**L.FAMILIES, **L.LATER_FAMILIES, **L.NEWER_FAMILIES} and FAMILY not in L.families() and len(L.families()) == 15
-    assert list(L.all_families()) == [*L.families(), FAMILY]
-    assert os.path.samefile(L.header_path(FAMILY), os.path.join(ROOT, "include", "sifsr_rloss.h"))
-    assert L.declared(FAMILY) == NAMES
-    assert L.call("sifsr_abi_version") == L.ABI_VERSION == 3 and len(L.COUNT_RETURNING) == 14
-
-
-def test_exported_symbols_are_the_declared_ones(L):
-    names = L.declared(FAMILY)
-    assert names and not [n for n in names if not n.startswith(PREFIX)]
-    assert not [n for n in names if "sifsr_" in n]                           # outside the core header's export check
-    for other, (_, op) in L.families().items():
-        assert not PREFIX.startswith(op) and not op.startswith(PREFIX), other
-        assert not set(names) & set(L.declared(other)), other
-        assert not [n for n in names if n.startswith(op)], other
-        assert not [n for n in L.declared(other) if n.startswith(PREFIX)], other
-    under = {n for n in exported(L.LIB_PATH) if n.startswith(PREFIX)}
-    assert under == set(names), f"exported but not declared, or declared but not exported: {sorted(under ^ set(names))}"
-    handle = ctypes.CDLL(L.LIB_PATH)
-    assert not [n for n in names if not hasattr(handle, n)]
-    assert not [n for n in names if not hasattr(L.lib(), n)]                # the binding carries the family
-    for n in names:
-        fn = getattr(L.lib(), n)
-        assert fn.restype is (ctypes.c_size_t if n in HOST_ONLY else ctypes.c_int) and fn.argtypes, n
-    assert not set(names) & L.COUNT_RETURNING
+def test_the_row_and_the_declared_names(L):
+    assert L.FAMILIES["rloss"] == ("sifsr_rloss.h", "sifsrq_")
+    assert L.declared("rloss") == NAMES
+    decls = L.parse_header(L.header_path("rloss"))
+    assert {n for n in NAMES if decls[n][0] is ctypes.c_size_t} == HOST_ONLY     # every other one returns an int status
+    assert not set(NAMES) & L.COUNT_RETURNING and len(L.COUNT_RETURNING) == 14
 
 
 def test_every_writing_entry_point_has_contract_cases(L):
     T = importlib.import_module("tests.test_rloss_gpu")
-    writers, covered = L.writers(FAMILY), set(T.CONTRACT)
-    assert writers == WRITERS and "stream" not in sum(writers.values(), [])
-    assert set(L.declared(FAMILY)) - set(writers) == HOST_ONLY               # the only entry point without a case
-    assert covered == set(writers), f"CONTRACT of tests/test_rloss_gpu.py and the writers differ: {sorted(covered ^ set(writers))}"
+    writers = L.writers("rloss")
+    assert writers == WRITERS
+    assert set(L.declared("rloss")) - set(writers) == HOST_ONLY              # the only entry point without a case
     for name, cases in T.CONTRACT.items():
         assert len(cases) >= 3, name
     # masked and unmasked, dsr NULL and given, a multi-tile ragged shape, both kinds
@@ -193,7 +167,7 @@ def test_every_writing_entry_point_has_contract_cases(L):
     assert {c[1] for c in cases} == {"sr2", "sr1"} and {c[2] for c in cases} >= {None, "blobs30"} and {c[3] for c in cases} == {False, True}
     assert any(c[0] in ((96, 120, 3.0), (80, 200, 2.5)) for c in cases) and any(c[0][2] == Q.MAX_FACTOR for c in cases)
     # the const inputs are declared const: run_contract's arena checks them untouched
-    decls = L.parse_header(L.header_path(FAMILY))
+    decls = L.parse_header(L.header_path("rloss"))
     consts = {n: [a[0] for a in decls[n][1] if a.pointer and a.const] for n in writers}
     assert consts == {"sifsrq_valid_counts": ["valid"], "sifsrq_sif_loss": ["sr", "lst", "valid", "counts2", "ndvi"]}
 

@@ -5,8 +5,8 @@
     cotangents it regenerates from their seeds; the adjoint identity in float64,
   * stencil monotonicity and contiguity over a sweep of sides, factors, half widths and crops: what the device's range table
     (one run of outputs per input pixel, found by bisection) rests on,
-  * the gate of the `sifsrt_` entry points of include/sifsr_sensor.h, the one row of sifsr._lib.LATER_FAMILIES, with the checks
-    tests/test_capi_gate.py applies to a row of FAMILIES,
+  * the pins of include/sifsr_sensor.h for the `sifsrt_` entry points (the gate itself is tests/test_capi_gate.py): the row, the
+    declared names, the writers, which entry points are host only, and what the memory-contract cases of tests/test_sensor_gpu.py cover,
   * the public names of sifsr.sensor and the error paths that need no GPU."""
 import ctypes
 import importlib
@@ -20,7 +20,7 @@ import torch
 
 from tests import degrade_reference as R
 from tests import sensor_reference as SR
-from tests.capi_host import L, exported  # noqa: F401  (L is the fixture)
+from tests.capi_host import L  # noqa: F401  (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "golden_sensor_v1.npz")
@@ -158,8 +158,7 @@ def test_stencils_are_monotone_and_each_pixel_is_read_by_one_run_of_outputs():
     assert seen >= 900 and longest > 2 * 16 + 4                       # no small fixed bound: longer than any window K
 
 
-# ---- 3. the gate of the second header table -------------------------------------------------------------------------------------
-FAMILY, PREFIX = "sensor", "sifsrt_"
+# ---- 3. the pins of include/sifsr_sensor.h (the gate itself is tests/test_capi_gate.py) ------------------------------------------
 NAMES = ["sifsrt_degrade_bwd", "sifsrt_degrade_bwd_workspace_bytes", "sifsrt_lowpass_bwd", "sifsrt_lowpass_fwd",
          "sifsrt_lowpass_workspace_bytes"]
 WRITERS = {"sifsrt_degrade_bwd": ["dx", "workspace"], "sifsrt_lowpass_fwd": ["out", "workspace"],
@@ -167,39 +166,19 @@ WRITERS = {"sifsrt_degrade_bwd": ["dx", "workspace"], "sifsrt_lowpass_fwd": ["ou
 HOST_ONLY = {"sifsrt_degrade_bwd_workspace_bytes", "sifsrt_lowpass_workspace_bytes"}   # no pointer at all: a size on the host
 
 
-def test_the_second_table(L):
-    assert L.LATER_FAMILIES == {FAMILY: ("sifsr_sensor.h", PREFIX)} and FAMILY not in L.FAMILIES and len(L.FAMILIES) == 13
-    assert os.path.samefile(L.header_path(FAMILY), os.path.join(ROOT, "include", "sifsr_sensor.h"))
-    assert L.declared(FAMILY) == NAMES
-    assert L.call("sifsr_abi_version") == L.ABI_VERSION == 3
-
-
-def test_exported_symbols_are_the_declared_ones(L):
-    names = L.declared(FAMILY)
-    assert names and not [n for n in names if not n.startswith(PREFIX)]
-    assert not [n for n in names if "sifsr_" in n]                           # outside the core header's export check
-    others = tuple(p for _, p in L.FAMILIES.values())
-    assert not PREFIX.startswith(others) and not [n for n in names if n.startswith(others)]
-    for family in L.FAMILIES:
-        assert not set(names) & set(L.declared(family)), family
-        assert not [n for n in L.declared(family) if n.startswith(PREFIX)], family
-    under = {n for n in exported(L.LIB_PATH) if n.startswith(PREFIX)}
-    assert under == set(names), f"exported but not declared, or declared but not exported: {sorted(under ^ set(names))}"
-    handle = ctypes.CDLL(L.LIB_PATH)
-    assert not [n for n in names if not hasattr(handle, n)]
-    assert not [n for n in names if not hasattr(L.lib(), n)]                # the binding carries the family
-    for n in names:
-        fn = getattr(L.lib(), n)
-        assert fn.restype is (ctypes.c_size_t if n in HOST_ONLY else ctypes.c_int) and fn.argtypes, n
-    assert not set(names) & L.COUNT_RETURNING
+def test_the_row_and_the_declared_names(L):
+    assert L.FAMILIES["sensor"] == ("sifsr_sensor.h", "sifsrt_")
+    assert L.declared("sensor") == NAMES
+    decls = L.parse_header(L.header_path("sensor"))
+    assert {n for n in NAMES if decls[n][0] is ctypes.c_size_t} == HOST_ONLY     # every other one returns an int status
+    assert not set(NAMES) & L.COUNT_RETURNING
 
 
 def test_every_writing_entry_point_has_a_contract_case(L):
     T = importlib.import_module("tests.test_sensor_gpu")
-    writers, covered = L.writers(FAMILY), set(T.CONTRACT)
-    assert writers == WRITERS and "stream" not in sum(writers.values(), [])
-    assert set(L.declared(FAMILY)) - set(writers) == HOST_ONLY               # the only entry points without a case
-    assert covered == set(writers), f"CONTRACT of tests/test_sensor_gpu.py and the writers differ: {sorted(covered ^ set(writers))}"
+    writers = L.writers("sensor")
+    assert writers == WRITERS
+    assert set(L.declared("sensor")) - set(writers) == HOST_ONLY             # the only entry points without a case
     for name, cases in T.CONTRACT.items():
         assert len(cases) >= 3, name
     # with and without out_valid, crop off and on, more than one image, the smallest shape of each operator
@@ -208,7 +187,7 @@ def test_every_writing_entry_point_has_a_contract_case(L):
     assert (1, 4, 4, R.FINE, 0, False, False, False) in [tuple(s) for s in shapes]
     assert any(h == hw + 1 or w == hw + 1 for _, h, w, _, hw in T.LOWPASS_CONTRACT_SHAPES)
     # the const inputs are declared const: run_contract's arena checks them untouched
-    decls = L.parse_header(L.header_path(FAMILY))
+    decls = L.parse_header(L.header_path("sensor"))
     for name in writers:
         consts = [a[0] for a in decls[name][1] if a.pointer and a.const]
         assert consts == (["dout", "out_valid"] if name == "sifsrt_degrade_bwd" else ["x"] if name == "sifsrt_lowpass_fwd" else ["dout"])
