@@ -9,7 +9,7 @@ and leave the buffers alone -- ``model.eval()`` afterwards predicts with exactly
     frozen_bn        context manager: bn_frozen + train() inside, both restored after
     input_gradient   dL/dx for an upstream gradient (sensitivity maps dSR/dNDVI, dSR/dLST), frozen statistics
     tile_targets     normalised LR targets, validity tiles and the valid count of a batch of active tiles, on the device
-    adapt_granule    fill -> select -> ONE read of the active count -> network inputs once -> `steps` masked training steps
+    adapt_granule    fill -> select -> ONE read of the active count -> network inputs once -> `steps` masked training steps (``_adapt``)
 
 CPU-only use raises SifsrError: there is no fallback.
 """
@@ -114,18 +114,27 @@ def adapt_granule(model, lst_g, ndvi_g, stats, mask=None, steps=20, lr=1e-5, alp
     _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
     if lst_g.dim() != 2:
         raise _lib.SifsrError(f"lst granule: expected a 2-D raster, got {tuple(lst_g.shape)}")
-    pipeline._mosaic_tiles(lst_g.shape, ndvi_g.shape, window, overlap, cover_edges)       # (raises before any launch)
+    lay = gaps._tile_layout(lst_g.shape, ndvi_g.shape, window, overlap, cover_edges)           # (raises before any launch)
     if int(batch) < 1 or int(steps) < 0:
         raise _lib.SifsrError(f"batch must be positive and steps non-negative, got {batch}, {steps}")
-    steps, batch = int(steps), int(batch)
+
+    def step(model, optimizer, lst, xb, vt, n_valid):
+        return train.train_step(model, optimizer, lst, xb[:, 0:1], xb[:, 1:2], stats, alpha, gamma, kind, valid=vt, n_valid=n_valid)
+
+    return _adapt(model, lay, step, lst_g, ndvi_g, stats, mask, int(steps), int(batch), lr, optimizer)
+
+
+def _adapt(model, lay, step, lst_g, ndvi_g, stats, mask, steps, batch, lr, optimizer):
+    """The loop of ``adapt_granule`` here and in ``rloss`` on the ``_granule.Layout`` ``lay``: fill -> select -> one read of the active
+    count -> the inputs of the active tiles once -> ``steps`` x ``step(model, optimizer, lst, xb, vt, n_valid)`` -> (ds, pl, loss)."""
     filled, valid = gaps.fill_gaps(lst_g, mask)
-    _, active, n_active = gaps.select_tiles(valid, window, overlap, cover_edges)
+    _, active, n_active = gaps.select_tiles(valid, lay.window, lay.overlap, lay.cover_edges)
     n = int(n_active.item())                                            # the one host sync
     losses = torch.zeros((steps, 3), dtype=torch.float32, device=lst_g.device)
     if n == 0 or steps == 0:
         return Adaptation(model, None, losses[:0] if n == 0 else losses, n, optimizer)
     start = model.flat_parameters().detach().clone()
-    x = gaps.prepare_active_tiles(filled, ndvi_g, stats, active, n_active, n, window, overlap, cover_edges)
+    x = lay.prepare_active(filled, ndvi_g, stats, active, n_active, n)
     if optimizer is None:
         optimizer = FlatAdam(model.parameters(), lr=lr)
     b = min(batch, n)
@@ -134,8 +143,7 @@ def adapt_granule(model, lst_g, ndvi_g, stats, mask=None, steps=20, lr=1e-5, alp
             first = (i * batch) % n
             idx = (torch.arange(first, first + b, device=x.device) % n) if first + b > n else slice(first, first + b)
             xb = x[idx]
-            lst, vt, n_valid = tile_targets(filled, valid, active, n_active, first, b, stats, window, overlap, cover_edges)
-            ds, pl, loss = train.train_step(model, optimizer, lst, xb[:, 0:1], xb[:, 1:2], stats, alpha, gamma, kind,
-                                            valid=vt, n_valid=n_valid)
+            lst, vt, n_valid = tile_targets(filled, valid, active, n_active, first, b, stats, lay.window, lay.overlap, lay.cover_edges)
+            ds, pl, loss = step(model, optimizer, lst, xb, vt, n_valid)
             losses[i, 0] = ds.detach(); losses[i, 1] = pl.detach(); losses[i, 2] = loss.detach()
     return Adaptation(model, start, losses, n, optimizer)

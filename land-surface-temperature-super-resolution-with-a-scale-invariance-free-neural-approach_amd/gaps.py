@@ -8,8 +8,9 @@ that are all cloud or sea, and returns no mask.  Here, on the device:
     fill_gaps             valid = finite, non-zero and kept by ``mask``; invalid pixels get the mean of the valid pixels of the
                           smallest aligned dyadic block around them that holds one (a push-pull pyramid, bit-defined)
     select_tiles          the tiles of the layout of ``pipeline.tile_origins`` that hold a valid pixel, in order
-    predict_granule_gaps  fill -> select -> ONE read of the active count -> network input of the active tiles only ->
-                          ceil(n_active / batch) forwards -> blend as ``predict_granule`` does, ``fill_value`` where invalid
+    predict_granule_gaps  ``_granule.predict_gaps`` on the x4 layout record of ``_tile_layout`` (``ratio`` runs it on its own): fill -> select
+                          -> ONE read of the active count -> network input of the active tiles only -> ceil(n_active / batch)
+                          forwards -> blend as ``predict_granule`` does, ``fill_value`` where invalid
 
 A valid pixel is blended from exactly the tiles the ungapped path uses (every tile covering a valid pixel is active), so at
 valid pixels ``predict_granule_gaps(gappy)`` equals ``predict_granule(filled)`` bit for bit, and a gap-free raster gives
@@ -19,7 +20,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, pipeline
+from . import _granule, _lib, pipeline
 from .conserve import granule_option
 
 
@@ -27,8 +28,8 @@ def _valid_raster(valid, shape, device, what="valid"):
     """-> a uint8 view of a (h, w) uint8 / bool device raster (one byte per pixel, non-zero = keep)"""
     if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.uint8, torch.bool):
         raise _lib.SifsrError(f"{what} must be a uint8 or bool tensor, got {getattr(valid, 'dtype', type(valid).__name__)}")
-    if not valid.is_cuda or valid.device != device:
-        raise _lib.SifsrError(f"{what} is on {valid.device}, the raster on {device}")
+    if not valid.is_cuda or (device is not None and valid.device != device):
+        raise _lib.SifsrError(f"{what} is on {valid.device}, the raster on {device or 'a ROCm GPU'}")
     if tuple(valid.shape) != tuple(shape):
         raise _lib.SifsrError(f"{what} must be {tuple(shape)}, got {tuple(valid.shape)}")
     return valid.contiguous().view(torch.uint8)
@@ -80,8 +81,7 @@ def prepare_active_tiles(filled, ndvi_g, stats, active, n_active, cap, window=64
     h, w = filled.shape
     x = torch.empty((int(cap), 2, 4 * window, 4 * window), dtype=torch.float32, device=filled.device)
     _lib.call("sifsrg_tiles_prepare", filled, ndvi_g, x, active, n_active, int(cap), h, w, window, overlap, 1 if cover_edges else 0,
-              float(stats["mean_lst"]), float(stats["std_lst"]), float(stats["mean_ndvi"]), float(stats["std_ndvi"]),
-              1 if clip_ndvi else 0, _lib.stream_ptr(filled.device))
+              *pipeline._stats4(stats), 1 if clip_ndvi else 0, _lib.stream_ptr(filled.device))
     return x
 
 
@@ -100,6 +100,18 @@ def blend_active_tiles(sr, slot, valid, window, stats, overlap=0, cover_edges=Fa
     _lib.call("sifsrg_tiles_blend", sr, slot, valid, out, h, w, window, overlap, 1 if cover_edges else 0, float(stats["mean_lst"]),
               float(stats["std_lst"]), float(fill_value), _lib.stream_ptr(sr.device))
     return out
+
+
+def _tile_layout(lst_shape, ndvi_shape, window, overlap, cover_edges, plain=False):
+    """-> the x4 ``_granule.Layout`` of an LST raster, or SifsrError; ``plain``: ``predict_granule``'s rule for its default layout"""
+    tiles = (pipeline._granule_tiles if plain else pipeline._mosaic_tiles)(lst_shape, ndvi_shape, window, overlap, cover_edges)
+    (h, w), lay = (int(v) for v in lst_shape), (overlap, cover_edges)
+    return _granule.Layout(
+        window, 4 * window, overlap, cover_edges, tiles, (4 * h, 4 * w),
+        lambda lst_g, ndvi_g, stats, out=None: pipeline.granule_to_tiles(lst_g, ndvi_g, stats, window, True, *lay, out)[0],
+        lambda filled, ndvi_g, stats, active, n_active, cap: prepare_active_tiles(filled, ndvi_g, stats, active, n_active, cap, window, *lay),
+        lambda sr, stats, out=None: pipeline.blend_tiles(sr, (h, w), window, stats, *lay, out),
+        lambda sr, slot, valid, stats, fill_value: blend_active_tiles(sr, slot, valid, window, stats, *lay, fill_value))
 
 
 @granule_option
@@ -125,22 +137,8 @@ def predict_granule_gaps(model, lst_g, ndvi_g, stats, mask=None, window=64, batc
     _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
     if lst_g.dim() != 2:
         raise _lib.SifsrError(f"lst granule: expected a 2-D raster, got {tuple(lst_g.shape)}")
-    ty, tx = pipeline._mosaic_tiles(lst_g.shape, ndvi_g.shape, window, overlap, cover_edges)       # (raises before any launch)
+    lay = _tile_layout(lst_g.shape, ndvi_g.shape, window, overlap, cover_edges)                          # (raises before any launch)
     if int(batch) < 1:
         raise _lib.SifsrError(f"batch must be positive, got {batch}")
     model.eval()
-    h, w = lst_g.shape
-    filled, valid = fill_gaps(lst_g, mask)
-    slot, active, n_active = select_tiles(valid, window, overlap, cover_edges)
-    n = int(n_active.item())                                            # the one host sync
-    if n == 0:
-        out = torch.full((4 * h, 4 * w), float(fill_value), dtype=torch.float32, device=lst_g.device)
-    else:
-        x = prepare_active_tiles(filled, ndvi_g, stats, active, n_active, n, window, overlap, cover_edges)
-        sr = torch.empty((n, 1, 4 * window, 4 * window), dtype=torch.float32, device=x.device)
-        for i in range(0, n, batch):
-            sr[i:i + batch] = model(x[i:i + batch])
-        out = blend_active_tiles(sr, slot, valid, window, stats, overlap, cover_edges, fill_value)
-    if return_info:
-        return out, {"valid": valid.bool(), "n_active": n, "n_tiles": ty * tx}
-    return out
+    return _granule.predict_gaps(model, lay, lst_g, ndvi_g, stats, mask, batch, fill_value, return_info)

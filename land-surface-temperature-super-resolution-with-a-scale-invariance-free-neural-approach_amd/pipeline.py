@@ -21,6 +21,21 @@ from . import _lib
 _UNIT = {"mean_lst": 0.0, "std_lst": 1.0, "mean_ndvi": 0.0, "std_ndvi": 1.0}
 
 
+def _stats4(stats):
+    """the four floats every prepare call ends its scalars with"""
+    return float(stats["mean_lst"]), float(stats["std_lst"]), float(stats["mean_ndvi"]), float(stats["std_ndvi"])
+
+
+def _tile_buffer(out, n, planes, hr, device, what):
+    """-> (n,planes,hr,hr) float32: new, or the first n tiles of the buffer ``out`` (a captured run's static one)"""
+    if out is None:
+        return torch.empty((n, planes, hr, hr), dtype=torch.float32, device=device)
+    _lib.require_gpu(out, what)
+    if out.dim() != 4 or out.shape[0] < n or tuple(out.shape[1:]) != (planes, hr, hr):
+        raise _lib.SifsrError(f"{what} must hold {(n, planes, hr, hr)}, got {tuple(out.shape)}")
+    return out[:n]
+
+
 def prepare_tiles(lst, ndvi, stats=None, clip_ndvi=False):
     """lst (T,1,w,w), ndvi (T,1,4w,4w) -> model input (T,2,4w,4w) = cat(bicubic4(z(lst)), z(clip(ndvi))).
     ``stats=None``: inputs are already normalised (the training DataLoader's tensors)."""
@@ -28,10 +43,9 @@ def prepare_tiles(lst, ndvi, stats=None, clip_ndvi=False):
     T, c, w, w2 = lst.shape
     if c != 1 or w != w2 or tuple(ndvi.shape) != (T, 1, 4 * w, 4 * w):
         raise _lib.SifsrError(f"prepare_tiles expects lst (T,1,w,w) and ndvi (T,1,4w,4w); got {tuple(lst.shape)}, {tuple(ndvi.shape)}")
-    st = stats or _UNIT
     x = torch.empty((T, 2, 4 * w, 4 * w), dtype=torch.float32, device=lst.device)
-    _lib.call("sifsr_tiles_prepare", lst, ndvi, x, T, 1, w, 0, 0, 0, float(st["mean_lst"]), float(st["std_lst"]),
-              float(st["mean_ndvi"]), float(st["std_ndvi"]), 1 if clip_ndvi else 0, _lib.stream_ptr(lst.device))
+    _lib.call("sifsr_tiles_prepare", lst, ndvi, x, T, 1, w, 0, 0, 0, *_stats4(stats or _UNIT), 1 if clip_ndvi else 0,
+              _lib.stream_ptr(lst.device))
     return x
 
 
@@ -70,6 +84,19 @@ def _mosaic_tiles(lst_shape, ndvi_shape, window, overlap, cover_edges):
     return len(tile_origins(h, window, overlap, cover_edges)), len(tile_origins(w, window, overlap, cover_edges))
 
 
+def _granule_tiles(lst_shape, ndvi_shape, window, overlap, cover_edges):
+    """``_mosaic_tiles``, or for the default layout the full tiles of predict.py:84-95 -> (tiles_y, tiles_x)."""
+    if overlap or cover_edges:
+        return _mosaic_tiles(lst_shape, ndvi_shape, window, overlap, cover_edges)
+    h, w = (int(v) for v in lst_shape)
+    if tuple(ndvi_shape) != (4 * h, 4 * w):
+        raise _lib.SifsrError("ndvi granule must be 4x the LST granule")
+    ty, tx = h // window, w // window
+    if ty < 1 or tx < 1:
+        raise _lib.SifsrError("granule smaller than one window")
+    return ty, tx
+
+
 def granule_to_tiles(lst_g, ndvi_g, stats, window=64, clip_ndvi=True, overlap=0, cover_edges=False, out=None):
     """Raw granule rasters lst_g (h,w) [K] and ndvi_g (4h,4w) -> (x (T,2,4win,4win), (tiles_y, tiles_x)).  Defaults: the
     non-overlapping full tiles of predict.py:84-95 (ragged edge tiles are skipped, as in the reference).  ``overlap`` /
@@ -78,30 +105,14 @@ def granule_to_tiles(lst_g, ndvi_g, stats, window=64, clip_ndvi=True, overlap=0,
     static input); the first T tiles of it are returned."""
     _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
     h, w = lst_g.shape
-
-    def alloc(T):
-        if out is None:
-            return torch.empty((T, 2, 4 * window, 4 * window), dtype=torch.float32, device=lst_g.device)
-        _lib.require_gpu(out, "tile buffer")
-        if out.dim() != 4 or out.shape[0] < T or tuple(out.shape[1:]) != (2, 4 * window, 4 * window):
-            raise _lib.SifsrError(f"tile buffer must hold {(T, 2, 4 * window, 4 * window)}, got {tuple(out.shape)}")
-        return out[:T]
-
+    ty, tx = _granule_tiles((h, w), ndvi_g.shape, window, overlap, cover_edges)
+    x = _tile_buffer(out, ty * tx, 2, 4 * window, lst_g.device, "tile buffer")
     if overlap or cover_edges:
-        ty, tx = _mosaic_tiles((h, w), ndvi_g.shape, window, overlap, cover_edges)
-        x = alloc(ty * tx)
-        _lib.call("sifsrx_tiles_prepare", lst_g, ndvi_g, x, h, w, window, overlap, 1 if cover_edges else 0,
-                  float(stats["mean_lst"]), float(stats["std_lst"]), float(stats["mean_ndvi"]), float(stats["std_ndvi"]),
+        _lib.call("sifsrx_tiles_prepare", lst_g, ndvi_g, x, h, w, window, overlap, 1 if cover_edges else 0, *_stats4(stats),
                   1 if clip_ndvi else 0, _lib.stream_ptr(lst_g.device))
-        return x, (ty, tx)
-    if tuple(ndvi_g.shape) != (4 * h, 4 * w):
-        raise _lib.SifsrError("ndvi granule must be 4x the LST granule")
-    ty, tx = h // window, w // window
-    if ty < 1 or tx < 1:
-        raise _lib.SifsrError("granule smaller than one window")
-    x = alloc(ty * tx)
-    _lib.call("sifsr_tiles_prepare", lst_g, ndvi_g, x, ty, tx, window, h, w, 1, float(stats["mean_lst"]), float(stats["std_lst"]),
-              float(stats["mean_ndvi"]), float(stats["std_ndvi"]), 1 if clip_ndvi else 0, _lib.stream_ptr(lst_g.device))
+    else:
+        _lib.call("sifsr_tiles_prepare", lst_g, ndvi_g, x, ty, tx, window, h, w, 1, *_stats4(stats), 1 if clip_ndvi else 0,
+                  _lib.stream_ptr(lst_g.device))
     return x, (ty, tx)
 
 
@@ -175,6 +186,5 @@ def scale_invariance_inputs(lst, ndvi, stats):
       lst_4km_up = (bicubic x4 of lst_4km - mean) / std"""
     ndvi_1km = decimate4_bic(ndvi)
     lst_4km = l4pool4(lst * stats["std_lst"] + stats["mean_lst"])
-    x = prepare_tiles(lst_4km, ndvi_1km, {"mean_lst": stats["mean_lst"], "std_lst": stats["std_lst"], "mean_ndvi": 0.0,
-                                          "std_ndvi": 1.0})
+    x = prepare_tiles(lst_4km, ndvi_1km, {**_UNIT, "mean_lst": stats["mean_lst"], "std_lst": stats["std_lst"]})
     return x[:, 0:1], x[:, 1:2], lst

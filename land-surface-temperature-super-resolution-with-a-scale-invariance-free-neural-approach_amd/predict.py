@@ -3,9 +3,10 @@
 The reference runs one eval-mode forward per 64x64 LST tile (batch 1) and de-normalises with
 ``* std + mean``; tiles are independent and do not overlap, so here they are stacked and pushed
 through the network in large batches (config 4 of BASELINE.json: batch 256).  ``predict_granule`` can also lay the
-tiles with an overlap and a last tile flush to each edge and blend them (a seamless, complete raster; not in the reference).  HDF/GeoTIFF I/O is out
-of scope; inputs are the already normalised ``lst_up`` / ``ndvi`` tiles.  ``predict_granule_gaps`` (sifsr/gaps.py)
-is ``predict_granule`` for granules with cloud / ocean / fill pixels: gaps filled, all-gap tiles skipped, the output masked.
+tiles with an overlap and a last tile flush to each edge and blend them (a seamless, complete raster; not in the reference); it and
+``GranulePredictor`` run ``_granule.predict``, shared with ``ratio.predict_granule``, on the x4 layout.  HDF/GeoTIFF I/O is out of
+scope; inputs are the already normalised ``lst_up`` / ``ndvi`` tiles.  ``predict_granule_gaps`` (sifsr/gaps.py) is
+``predict_granule`` for granules with cloud / ocean / fill pixels: gaps filled, all-gap tiles skipped, the output masked.
 ``conserve=k`` on the granule calls adds k residual-correction steps after the blend (sifsr/conserve.py): the
 output, seen through the sensor's MTF and decimated by 4, then returns the LST raster it was predicted from; 0, the default,
 leaves every bit as it was.
@@ -14,8 +15,9 @@ from __future__ import annotations
 
 import torch
 
+from . import _granule, _lib
 from .conserve import granule_option
-from .gaps import fill_gaps, predict_granule_gaps, select_tiles  # noqa: F401  (the gap-aware path)
+from .gaps import _tile_layout, fill_gaps, predict_granule_gaps, select_tiles  # noqa: F401  (the gap-aware path)
 
 
 @torch.inference_mode()
@@ -26,32 +28,6 @@ def predict_tiles(model, lst_up, ndvi, stats, batch=256):
     for i in range(0, lst_up.shape[0], batch):
         x = torch.cat((lst_up[i:i + batch], ndvi[i:i + batch]), dim=1)
         out[i:i + batch] = model(x) * stats["std_lst"] + stats["mean_lst"]
-    return out
-
-
-def _granule_forward(model, lst_g, ndvi_g, stats, window, batch, overlap, cover_edges, x=None, sr=None, out=None, conserve=0):
-    """prepare -> batched eval forwards -> blend, all enqueued on the current stream.  x / sr / out: static buffers of a
-    captured run (x and sr hold a whole number of batches: the tiles past the last real one are zeros and their predictions
-    are never read); None: allocated here and the last batch is as short as it is.  conserve: that many correction steps on the
-    blended raster, in place, on the same stream (``conserve.conserve``; its scratch is allocated here, in a captured run from the
-    graph's own pool)."""
-    from . import conserve as _conserve, pipeline
-    if int(conserve) < 0:
-        raise pipeline._lib.SifsrError(f"conserve must be a step count >= 0, got {conserve}")
-    h, w = lst_g.shape
-    if x is None:
-        x, _ = pipeline.granule_to_tiles(lst_g, ndvi_g, stats, window=window, clip_ndvi=True, overlap=overlap,
-                                         cover_edges=cover_edges)
-        sr = torch.empty((x.shape[0], 1, 4 * window, 4 * window), dtype=torch.float32, device=x.device)
-        n = x.shape[0]
-    else:
-        n = pipeline.granule_to_tiles(lst_g, ndvi_g, stats, window=window, clip_ndvi=True, overlap=overlap,
-                                      cover_edges=cover_edges, out=x)[0].shape[0]
-    for i in range(0, x.shape[0], batch):
-        sr[i:i + batch] = model(x[i:i + batch])
-    out = pipeline.blend_tiles(sr[:n], (h, w), window, stats, overlap, cover_edges, out=out)
-    if int(conserve) > 0:
-        _conserve.conserve(out, lst_g, None, n_iter=int(conserve), out=out)
     return out
 
 
@@ -70,7 +46,9 @@ def predict_granule(model, lst_g, ndvi_g, stats, window=64, batch=256, overlap=0
     Keyword-only ``conserve=k`` (``conserve.granule_option``): k steps of ``conserve.conserve`` on the blended raster (cells of
     0 K / non-finite LST pixels and the pixels no tile reached keep their bits); 0, the default: none."""
     model.eval()
-    return _granule_forward(model, lst_g, ndvi_g, stats, window, batch, overlap, cover_edges)
+    _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
+    lay = _tile_layout(lst_g.shape, ndvi_g.shape, window, overlap, cover_edges, plain=True)             # (raises before any launch)
+    return _granule.predict(model, lay, lst_g, ndvi_g, stats, batch)
 
 
 def tile_granule(lst_norm, ndvi_norm, window=64):
@@ -132,7 +110,6 @@ class GranulePredictor:
     graph cannot have a data-dependent batch count."""
 
     def __init__(self, model, lst_shape, stats, window=64, overlap=0, cover_edges=False, batch=256, device=None, conserve=0):
-        from . import pipeline
         self.model = model.eval()
         dev = device or next(model.parameters()).device
         h, w = (int(v) for v in lst_shape)
@@ -140,17 +117,12 @@ class GranulePredictor:
         self.overlap, self.cover_edges, self.batch = int(overlap), bool(cover_edges), int(batch)
         self.conserve = int(conserve)
         if self.conserve < 0:
-            raise pipeline._lib.SifsrError(f"conserve must be a step count >= 0, got {conserve}")
-        if self.overlap or self.cover_edges:
-            ty, tx = pipeline._mosaic_tiles((h, w), (4 * h, 4 * w), self.window, self.overlap, self.cover_edges)
-        else:
-            ty, tx = h // self.window, w // self.window
-            if ty < 1 or tx < 1:
-                raise pipeline._lib.SifsrError("granule smaller than one window")
+            raise _lib.SifsrError(f"conserve must be a step count >= 0, got {conserve}")
+        self.layout = _tile_layout((h, w), (4 * h, 4 * w), self.window, self.overlap, self.cover_edges, plain=True)
         if self.batch < 1:
-            raise pipeline._lib.SifsrError(f"batch must be positive, got {batch}")
-        self.tiles = (ty, tx)
-        n, hr = ty * tx, 4 * self.window
+            raise _lib.SifsrError(f"batch must be positive, got {batch}")
+        self.tiles = self.layout.tiles
+        n, hr = self.tiles[0] * self.tiles[1], self.layout.hr
         self.batch = min(self.batch, n)
         padded = -(-n // self.batch) * self.batch
         self.lst = torch.zeros((h, w), dtype=torch.float32, device=dev)
@@ -169,8 +141,8 @@ class GranulePredictor:
             self._run()
 
     def _run(self):
-        _granule_forward(self.model, self.lst, self.ndvi, self.stats, self.window, self.batch, self.overlap, self.cover_edges,
-                         x=self.x, sr=self.sr, out=self.out, conserve=self.conserve)
+        _granule.predict(self.model, self.layout, self.lst, self.ndvi, self.stats, self.batch, x=self.x, sr=self.sr, out=self.out,
+                         conserve=self.conserve)
 
     @torch.inference_mode()
     def __call__(self, lst_g, ndvi_g):

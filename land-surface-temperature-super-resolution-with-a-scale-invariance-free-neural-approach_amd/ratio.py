@@ -8,7 +8,7 @@ super-resolved raster comes out, seamless and gap-aware.
     prepare_tiles           the training-batch form: (T,1,w,w) and (T,1,P,P) -> (T,2,P,P)
     granule_to_tiles / blend_tiles / predict_granule / predict_granule_gaps
                             ``pipeline.granule_to_tiles`` / ``pipeline.blend_tiles`` / ``predict.predict_granule`` /
-                            ``gaps.predict_granule_gaps`` with the tile side ``hr`` as an argument
+                            ``gaps.predict_granule_gaps`` with the tile side ``hr`` as an argument, on the drivers of ``_granule``
 
 A tile is ``window`` LST pixels and ``hr`` network pixels on a side.  The rules (``sifsrr_geometry``): 1 <= window <= 64; hr a
 multiple of 8 in 24..256 with window < hr <= 16 window; with p / q = hr / window in lowest terms, both sides of the LST raster and
@@ -27,8 +27,8 @@ from collections import namedtuple
 
 import torch
 
-from . import _lib, gaps
-from .pipeline import _UNIT
+from . import _granule, _lib, gaps
+from .pipeline import _UNIT, _stats4, _tile_buffer
 
 Geometry = namedtuple("Geometry", "p q tiles hr_shape")
 MAX_LST_SIDE = 16384
@@ -63,6 +63,17 @@ def _layout(lst_g, ndvi_shape, window, hr, overlap, cover_edges):
         raise _lib.SifsrError(f"ndvi granule must be {g.hr_shape} ({g.p}/{g.q} of the LST granule {tuple(lst_g.shape)}), got "
                               f"{tuple(ndvi_shape)}")
     return g
+
+
+def _tile_layout(lst_g, ndvi_shape, window, hr, overlap, cover_edges):
+    """-> the ``_granule.Layout`` at ratio hr / window of the raster ``lst_g``, or ``_layout``'s SifsrError"""
+    g, shape, lay = _layout(lst_g, ndvi_shape, window, hr, overlap, cover_edges), lst_g.shape, (overlap, cover_edges)
+    return _granule.Layout(
+        window, hr, overlap, cover_edges, g.tiles, g.hr_shape,
+        lambda lst_g, ndvi_g, stats, out=None: granule_to_tiles(lst_g, ndvi_g, stats, window, hr, True, *lay, out)[0],
+        lambda filled, ndvi_g, stats, active, n_active, cap: prepare_active_tiles(filled, ndvi_g, stats, active, n_active, cap, window, hr, *lay),
+        lambda sr, stats, out=None: blend_tiles(sr, shape, window, hr, stats, *lay, out),
+        lambda sr, slot, valid, stats, fill_value: blend_active_tiles(sr, slot, valid, window, hr, stats, *lay, fill_value))
 
 
 def upsample(x, size):
@@ -106,28 +117,13 @@ def prepare_tiles(lst, ndvi, stats=None, clip_ndvi=False):
         raise _lib.SifsrError(f"prepare_tiles expects lst (T,1,w,w) and ndvi (T,1,P,P); got {tuple(lst.shape)}, {tuple(ndvi.shape)}")
     T, w, P = lst.shape[0], lst.shape[2], ndvi.shape[2]
     geometry((w, w), w, P)
-    st = stats or _UNIT
     x = torch.empty((T, 2, P, P), dtype=torch.float32, device=lst.device)
     step = max(1, MAX_LST_SIDE // w)                                     # tiles per launch: a raster of (step w, w) LST pixels
     for b in range(0, T, step):
         n = min(step, T - b)
         _lib.call("sifsrr_tiles_prepare", lst[b:b + n], ndvi[b:b + n], x[b:b + n], None, None, n, n * w, w, w, P, 0, 0,
-                  float(st["mean_lst"]), float(st["std_lst"]), float(st["mean_ndvi"]), float(st["std_ndvi"]), 1 if clip_ndvi else 0,
-                  _lib.stream_ptr(lst.device))
+                  *_stats4(stats or _UNIT), 1 if clip_ndvi else 0, _lib.stream_ptr(lst.device))
     return x
-
-
-def _tile_buffer(out, n, planes, hr, device, what):
-    if out is None:
-        return torch.empty((n, planes, hr, hr), dtype=torch.float32, device=device)
-    _lib.require_gpu(out, what)
-    if out.dim() != 4 or out.shape[0] < n or tuple(out.shape[1:]) != (planes, hr, hr):
-        raise _lib.SifsrError(f"{what} must hold {(n, planes, hr, hr)}, got {tuple(out.shape)}")
-    return out[:n]
-
-
-def _stats4(stats):
-    return float(stats["mean_lst"]), float(stats["std_lst"]), float(stats["mean_ndvi"]), float(stats["std_ndvi"])
 
 
 def granule_to_tiles(lst_g, ndvi_g, stats, window, hr, clip_ndvi=True, overlap=0, cover_edges=False, out=None):
@@ -199,13 +195,6 @@ def blend_active_tiles(sr, slot, valid, window, hr, stats, overlap=0, cover_edge
     return out
 
 
-def _forwards(model, x, batch, hr):
-    sr = torch.empty((x.shape[0], 1, hr, hr), dtype=torch.float32, device=x.device)
-    for i in range(0, x.shape[0], batch):
-        sr[i:i + batch] = model(x[i:i + batch])
-    return sr
-
-
 @torch.inference_mode()
 def predict_granule(model, lst_g, ndvi_g, stats, window=64, hr=192, batch=256, overlap=0, cover_edges=False):
     """``predict.predict_granule`` at ratio ``hr / window``: raw LST raster (h,w) [K] + raw NDVI raster (h p/q, w p/q) ->
@@ -213,12 +202,11 @@ def predict_granule(model, lst_g, ndvi_g, stats, window=64, hr=192, batch=256, o
     through the network in eval mode in batches of ``batch``, then de-normalised and blended by another; ``overlap`` (LST pixels,
     a multiple of q, 0..window/2) and ``cover_edges`` are those of ``predict.predict_granule``."""
     _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
-    _layout(lst_g, ndvi_g.shape, window, hr, overlap, cover_edges)                            # (raises before any launch)
+    lay = _tile_layout(lst_g, ndvi_g.shape, window, hr, overlap, cover_edges)                 # (raises before any launch)
     if int(batch) < 1:
         raise _lib.SifsrError(f"batch must be positive, got {batch}")
     model.eval()
-    x, _ = granule_to_tiles(lst_g, ndvi_g, stats, window, hr, True, overlap, cover_edges)
-    return blend_tiles(_forwards(model, x, int(batch), hr), lst_g.shape, window, hr, stats, overlap, cover_edges)
+    return _granule.predict(model, lay, lst_g, ndvi_g, stats, int(batch))
 
 
 @torch.inference_mode()
@@ -236,20 +224,10 @@ def predict_granule_gaps(model, lst_g, ndvi_g, stats, mask=None, window=64, hr=1
 
     ``return_info``: also {"valid": bool (h,w) device tensor, "n_active": int, "n_tiles": int}."""
     _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
-    g = _layout(lst_g, ndvi_g.shape, window, hr, overlap, cover_edges)                        # (raises before any launch)
+    lay = _tile_layout(lst_g, ndvi_g.shape, window, hr, overlap, cover_edges)                 # (raises before any launch)
     if int(window) % 4:
         raise _lib.SifsrError(f"window must be a multiple of 4 for the tile selection, got {window}")
     if int(batch) < 1:
         raise _lib.SifsrError(f"batch must be positive, got {batch}")
     model.eval()
-    filled, valid = gaps.fill_gaps(lst_g, mask)
-    slot, active, n_active = gaps.select_tiles(valid, window, overlap, cover_edges)
-    n = int(n_active.item())                                            # the one host sync
-    if n == 0:
-        out = torch.full(g.hr_shape, float(fill_value), dtype=torch.float32, device=lst_g.device)
-    else:
-        x = prepare_active_tiles(filled, ndvi_g, stats, active, n_active, n, window, hr, overlap, cover_edges)
-        out = blend_active_tiles(_forwards(model, x, int(batch), hr), slot, valid, window, hr, stats, overlap, cover_edges, fill_value)
-    if return_info:
-        return out, {"valid": valid.bool(), "n_active": n, "n_tiles": g.tiles[0] * g.tiles[1]}
-    return out
+    return _granule.predict_gaps(model, lay, lst_g, ndvi_g, stats, mask, int(batch), fill_value, return_info)

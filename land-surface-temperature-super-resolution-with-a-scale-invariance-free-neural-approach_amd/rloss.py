@@ -4,8 +4,8 @@ a partly valid patch -- in one call with its gradient.
 
     valid_counts(valid, hr_shape)      (n1, n2) on the device: the valid LR cells and the HR pixels under them
     sif_loss_with_grad / sif_loss      the loss block at ``factor``, optionally over the valid cells only
-    train_step                         ``sensor.train_step`` with the fused loss, ``valid=`` for cloudy patches
-    adapt_granule                      ``adapt.adapt_granule`` at ratio hr / window
+    train_step                         ``sensor.train_step`` with the fused loss, ``valid=`` for cloudy patches (``train._optimise``)
+    adapt_granule                      ``adapt.adapt_granule`` at ratio hr / window: its own checks, then the same loop
 
 The LR cell of HR pixel (Y, X) is (Y h // H, X w // W): the rule under which ``ratio.predict_granule_gaps`` masks its output.
 Limits (``sifsrq_sif_loss``): 1 < factor <= 8, sides of ceil(factor) + 1 .. 16384, the half width of the sensor model at its
@@ -18,9 +18,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, adapt, gaps, ratio, sensor
-from . import distributed as dp
-from .optim import FlatAdam
+from . import _lib, adapt, gaps, ratio, sensor, train
 
 MAX_FACTOR = 8.0
 MAX_SIDE = 16384
@@ -40,14 +38,10 @@ def _factor(factor, what):
 
 
 def _lr_mask(valid, shape, device, what):
-    if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.uint8, torch.bool):
-        raise _lib.SifsrError(f"{what}: valid must be a uint8 or bool tensor, got {getattr(valid, 'dtype', type(valid).__name__)}")
+    """``gaps._valid_raster`` for one byte per LR cell: (B,1,h,w) or (B,h,w), on ``device`` (None: any GPU)"""
     B, h, w = shape
-    if tuple(valid.shape) not in ((B, 1, h, w), (B, h, w)):
-        raise _lib.SifsrError(f"{what}: valid must be {(B, 1, h, w)} (one byte per LR cell), got {tuple(valid.shape)}")
-    if not valid.is_cuda or (device is not None and valid.device != device):
-        raise _lib.SifsrError(f"{what}: valid is on {valid.device}: this package only runs on a ROCm GPU (gfx950); there is no CPU path.")
-    return valid.contiguous().view(torch.uint8)
+    want = (B, h, w) if tuple(getattr(valid, "shape", ())) == (B, h, w) else (B, 1, h, w)
+    return gaps._valid_raster(valid, want, device, f"{what}: valid")
 
 
 def valid_counts(valid, hr_shape):
@@ -174,19 +168,13 @@ def train_step(model, optimizer, lst, lst_up, ndvi, stats, alpha, gamma, factor,
     Works with ``model.bn_frozen``.  Under data parallelism each rank normalises by its own counts before the gradients are
     averaged, as ``train.train_step`` does.  Returns device scalars (ds_loss, percep_loss, loss) -- no host sync -- and, with
     ``return_sr``, the detached training-mode prediction."""
-    model.train()
-    optimizer.zero_grad(set_to_none=True)
-    sr = model(torch.cat((lst_up, ndvi), dim=1))
-    srd, lst, ndvi = sr.detach().contiguous(), lst.contiguous(), ndvi.contiguous()
-    k, B, H, W, f, valid, counts = _args(kind, srd, lst, ndvi, factor, valid, counts, "train_step")
-    losses, dsr = _call(k, srd, lst, ndvi, B, H, W, f, stats["mean_lst"], stats["std_lst"], alpha, gamma, valid, counts, True)
-    sr.backward(dsr)
-    if sync_grads:
-        dp.allreduce_gradients(model, optimizer)
-    optimizer.step()
-    if return_sr:
-        return losses[0], losses[1], losses[2], sr.detach()
-    return losses[0], losses[1], losses[2]
+    def loss_fn(sr):
+        srd, lst_c, ndvi_c = sr.detach().contiguous(), lst.contiguous(), ndvi.contiguous()
+        k, B, H, W, f, v, c = _args(kind, srd, lst_c, ndvi_c, factor, valid, counts, "train_step")
+        losses, dsr = _call(k, srd, lst_c, ndvi_c, B, H, W, f, stats["mean_lst"], stats["std_lst"], alpha, gamma, v, c, True)
+        return losses[0], losses[1], losses[2], dsr
+
+    return train._optimise(model, optimizer, lst_up, ndvi, loss_fn, sync_grads, return_sr)
 
 
 def adapt_granule(model, lst_g, ndvi_g, stats, window, hr, mask=None, steps=20, lr=1e-5, alpha=0.5, gamma=1.0, kind="sr2", batch=16,
@@ -218,30 +206,14 @@ def adapt_granule(model, lst_g, ndvi_g, stats, window, hr, mask=None, steps=20, 
         raise _lib.SifsrError(f"adapt_granule: at ratio {hr}/{window} the sensor model sees {got} of an {(hr, hr)} tile, not "
                               f"{(window, window)} (sensor.lr_shape: the crop of the sensor model cuts floor(ceil(factor) / factor) cells on "
                               "each side); choose a window and hr whose LR tile is the window")
-    ratio._layout(lst_g, ndvi_g.shape, window, hr, overlap, cover_edges)                       # (raises before any launch)
+    lay = ratio._tile_layout(lst_g, ndvi_g.shape, window, hr, overlap, cover_edges)            # (raises before any launch)
     if window % 4:
         raise _lib.SifsrError(f"window must be a multiple of 4 for the tile selection, got {window}")
     if int(batch) < 1 or int(steps) < 0:
         raise _lib.SifsrError(f"batch must be positive and steps non-negative, got {batch}, {steps}")
     _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
-    steps, batch = int(steps), int(batch)
-    filled, valid = gaps.fill_gaps(lst_g, mask)
-    _, active, n_active = gaps.select_tiles(valid, window, overlap, cover_edges)
-    n = int(n_active.item())                                            # the one host sync
-    losses = torch.zeros((steps, 3), dtype=torch.float32, device=lst_g.device)
-    if n == 0 or steps == 0:
-        return adapt.Adaptation(model, None, losses[:0] if n == 0 else losses, n, optimizer)
-    start = model.flat_parameters().detach().clone()
-    x = ratio.prepare_active_tiles(filled, ndvi_g, stats, active, n_active, n, window, hr, overlap, cover_edges)
-    if optimizer is None:
-        optimizer = FlatAdam(model.parameters(), lr=lr)
-    b = min(batch, n)
-    with adapt.frozen_bn(model):
-        for i in range(steps):
-            first = (i * batch) % n
-            idx = (torch.arange(first, first + b, device=x.device) % n) if first + b > n else slice(first, first + b)
-            xb = x[idx]
-            lst, vt, _ = adapt.tile_targets(filled, valid, active, n_active, first, b, stats, window, overlap, cover_edges)
-            out = train_step(model, optimizer, lst, xb[:, 0:1], xb[:, 1:2], stats, alpha, gamma, factor, kind=kind, valid=vt)
-            losses[i, 0] = out[0]; losses[i, 1] = out[1]; losses[i, 2] = out[2]
-    return adapt.Adaptation(model, start, losses, n, optimizer)
+
+    def step(model, optimizer, lst, xb, vt, n_valid):                       # (the fused loss forms its own counts from vt)
+        return train_step(model, optimizer, lst, xb[:, 0:1], xb[:, 1:2], stats, alpha, gamma, factor, kind=kind, valid=vt)
+
+    return adapt._adapt(model, lay, step, lst_g, ndvi_g, stats, mask, int(steps), int(batch), lr, optimizer)

@@ -7,7 +7,7 @@ scale-invariance-free loss needs when the ratio between the two sensors is not 4
                                 ``sifsrt_degrade_bwd``, the transpose of the same banded operator.
     lowpass(x, factor, mtf)     ``get_output_ftm(factor=f)`` (utils.py:1833-1860): the reflect-border Gaussian of the MTF at half
                                 width hkw or ceil(factor), forward and adjoint (``sifsrt_lowpass_fwd`` / ``_bwd``).
-    sif_loss / train_step       the loss block and the optimisation step of the two training scripts on top of them.
+    sif_loss / train_step       the loss block and the optimisation step (``train._optimise``) of the two training scripts on top of them.
 
 Everything is fp32 on the device, accumulated in float64 and rounded once; CPU tensors raise SifsrError: there is no CPU path.
 
@@ -19,8 +19,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, degrade
-from . import distributed as dp
+from . import _lib, degrade, train
 from .sif_ops import huber_loss, sobel_bank
 
 
@@ -163,15 +162,7 @@ def train_step(model, optimizer, lst, lst_up, ndvi, stats, alpha, gamma, factor,
     ``F.interpolate(lst, size=(H, W), mode="bicubic", align_corners=False)`` on the device (torch's own kernel); at x4 ``pipeline.bicubic_up4`` stays the
     path.  Works with ``model.bn_frozen`` as the ordinary step does.  Returns device scalars (ds_loss, percep_loss, loss) -- no host
     sync -- and, with ``return_sr``, the detached training-mode prediction."""
-    model.train()
-    optimizer.zero_grad(set_to_none=True)
-    sr = model(torch.cat((lst_up, ndvi), dim=1))
-    ds, pl, loss = sif_loss(kind, sr, lst, ndvi, factor, stats["mean_lst"], stats["std_lst"], alpha, gamma)
-    loss.backward()
-    if sync_grads:
-        dp.allreduce_gradients(model, optimizer)
-    optimizer.step()
-    loss = loss.detach()
-    if return_sr:
-        return ds, pl, loss, sr.detach()
-    return ds, pl, loss
+    mean, std = stats["mean_lst"], stats["std_lst"]
+    loss_fn = lambda sr: sif_loss(kind, sr, lst, ndvi, factor, mean, std, alpha, gamma) + (None,)   # (no dsr: loss.backward())
+    ds, pl, loss, *sr = train._optimise(model, optimizer, lst_up, ndvi, loss_fn, sync_grads, return_sr)
+    return (ds, pl, loss.detach(), *sr)

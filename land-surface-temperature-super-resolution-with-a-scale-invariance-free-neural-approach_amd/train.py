@@ -38,23 +38,31 @@ def train_step(model, optimizer, lst, lst_up, ndvi, stats, alpha, gamma, kind="s
     ``valid`` / ``n_valid`` (both or neither): the masked loss over the valid LST pixels only (module docstring)."""
     if (valid is None) != (n_valid is None):
         raise ValueError("train_step: pass both valid and n_valid, or neither")
+    mean, std = stats["mean_lst"], stats["std_lst"]
+    if valid is None:
+        loss_fn = lambda sr: sif_loss_with_grad(kind, sr, lst, ndvi, mean, std, alpha, gamma)
+    else:
+        loss_fn = lambda sr: masked_sif_loss_with_grad(kind, sr, lst, valid, n_valid, ndvi, mean, std, alpha, gamma)
+    return _optimise(model, optimizer, lst_up, ndvi, loss_fn, sync_grads, return_sr)
+
+
+def _optimise(model, optimizer, lst_up, ndvi, loss_fn, sync_grads=True, return_sr=False):
+    """The step under ``train_step``, ``si_train_step``, ``sensor.train_step`` and ``rloss.train_step`` (each: its checks and a loss
+    closure): ``loss_fn(sr)`` -> (ds, pl, loss, dsr) with dsr = d loss / d sr from a fused loss op (``sr.backward(dsr)`` ==
+    ``loss.backward()``) or None for a loss composed of autograd ops.  Only enqueues -- no allocation outside torch's pool, no
+    synchronisation, no host value that changes between steps --, so ``GraphedTrainStep`` and every other capture record through it."""
     model.train()
     optimizer.zero_grad(set_to_none=True)
-    lst_ndvi = torch.cat((lst_up, ndvi), dim=1)
-    sr = model(lst_ndvi)
-    # loss.backward() == sr.backward(d loss / d sr): the fused loss op returns that gradient directly (sif_ops.sif_loss_with_grad)
-    if valid is None:
-        ds, pl, loss, dsr = sif_loss_with_grad(kind, sr, lst, ndvi, stats["mean_lst"], stats["std_lst"], alpha, gamma)
+    sr = model(torch.cat((lst_up, ndvi), dim=1))
+    ds, pl, loss, dsr = loss_fn(sr)
+    if dsr is None:
+        loss.backward()
     else:
-        ds, pl, loss, dsr = masked_sif_loss_with_grad(kind, sr, lst, valid, n_valid, ndvi, stats["mean_lst"], stats["std_lst"],
-                                                      alpha, gamma)
-    sr.backward(dsr)
+        sr.backward(dsr)
     if sync_grads:
         dp.allreduce_gradients(model, optimizer)
     optimizer.step()
-    if return_sr:
-        return ds, pl, loss, sr.detach()
-    return ds, pl, loss
+    return (ds, pl, loss, sr.detach()) if return_sr else (ds, pl, loss)
 
 
 @torch.inference_mode()
@@ -84,15 +92,7 @@ def _unpack_batch(batch, device):
 def si_train_step(model, optimizer, lst_4km_up, ndvi_1km, lst_1km, sync_grads=True):
     """The scale-invariance baseline's step (train_model_B_scale_invariance.py:86-103): the model is trained one scale
     down (4 km -> 1 km, 64x64 patches) with a plain ``nn.HuberLoss`` against the 1 km LST.  Returns the device loss."""
-    model.train()
-    optimizer.zero_grad(set_to_none=True)
-    sr = model(torch.cat((lst_4km_up, ndvi_1km), dim=1))
-    loss = huber_loss(sr, lst_1km)
-    loss.backward()
-    if sync_grads:
-        dp.allreduce_gradients(model, optimizer)
-    optimizer.step()
-    return loss
+    return _optimise(model, optimizer, lst_4km_up, ndvi_1km, lambda sr: (None, None, huber_loss(sr, lst_1km), None), sync_grads)[2]
 
 
 class ModelCheckpoint:
