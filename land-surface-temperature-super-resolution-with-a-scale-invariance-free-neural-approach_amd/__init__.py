@@ -43,6 +43,9 @@ Drop-in surface (SURVEY.md §8 b):
   rloss.valid_counts / sif_loss / sif_loss_with_grad / train_step / adapt_granule  <- no counterpart: the SIF loss at any ratio as
                                        two fused kernels, masked (cloudy patches at x3, x2.5, x2), and fine-tuning on a granule at
                                        any ratio hr / window (include/sifsr_rloss.h)
+  rconserve.consistency / conserve, ratio.predict_granule(conserve=) / ratio.predict_granule_gaps(conserve=)  <- no counterpart:
+                                       the residual LST - D(SR) and its correction at any ratio H / h <= 8, with the sensor model of
+                                       degrade and the resampler of ratio (include/sifsr_rconserve.h)
   products.decode / PatchMiner / MinedPatches, dataset.MinedDataset  <- process_modis.py:38-335, data_preparation.py:32-102
                                        (raw granule arrays -> patches + statistics.json, on device)
 
@@ -53,7 +56,7 @@ and registers ``sifsr`` / ``sifsr.<submodule>`` as aliases of the same module ob
 import importlib
 import sys
 
-_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "degrade", "predict", "baselines", "products", "lpips", "adapt", "sensor", "ratio", "rloss")
+_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "degrade", "predict", "baselines", "products", "lpips", "adapt", "sensor", "rconserve", "ratio", "rloss")
 for _m in _SUBMODULES:
     importlib.import_module(__name__ + "." + _m)
 

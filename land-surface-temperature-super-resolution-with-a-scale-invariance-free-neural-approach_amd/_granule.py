@@ -29,8 +29,9 @@ def forwards(model, x, batch, sr=None):
 def predict(model, lay, lst_g, ndvi_g, stats, batch, x=None, sr=None, out=None, conserve=0):
     """prepare -> batched forwards -> blend.  x / sr / out: static buffers of a captured run (x and sr hold a whole number of
     batches: the tiles past the last real one are zeros and their predictions are never read); None: allocated here and the last
-    batch is as short as it is.  conserve (x4 only): that many ``conserve.conserve`` steps on the blended raster, in place (its
-    scratch is allocated here, in a captured run from the graph's own pool)."""
+    batch is as short as it is.  conserve (x4 only; at a ratio the option is ``rconserve.granule_option``, around the call): that
+    many ``conserve.conserve`` steps on the blended raster, in place (its scratch is allocated here, in a captured run from the
+    graph's own pool)."""
     if int(conserve) < 0:
         raise _lib.SifsrError(f"conserve must be a step count >= 0, got {conserve}")
     tiles = lay.prepare(lst_g, ndvi_g, stats, out=x)

@@ -37,6 +37,7 @@ FAMILIES = {
     "sensor": ("sifsr_sensor.h", "sifsrt_"),
     "ratio": ("sifsr_ratio.h", "sifsrr_"),
     "rloss": ("sifsr_rloss.h", "sifsrq_"),
+    "rconserve": ("sifsr_rconserve.h", "sifsrc_"),
 }
 ABI_VERSION = 3
 # the entry points whose int return is a count, not a status: call() raises on a non-zero int from every other one

@@ -83,14 +83,17 @@ def conserve(sr, lst, mask=None, n_iter=1, relax=1.0, mtf=0.1, out=None, return_
     return (out, stats) if return_stats else out
 
 
-def granule_option(fn):
+def granule_option(fn, correct=None):
     """Decorator that gives a whole-granule prediction call (``predict.predict_granule``, ``gaps.predict_granule_gaps``) the
     keyword-only option ``conserve=k``: k correction steps on the blended raster, in place, against the call's own ``lst_g`` (and
     ``mask``, where the call has one), on the same stream; with ``return_info`` the statistics go into the info dict as
     ``"conserve_stats"``.  ``conserve=0``, the default, is the undecorated call: the same launches, the same bits.  The option is
     added around the call and not to its parameter list: the positional signature of the two calls is part of their contract
-    (tests/test_gaps_host.py pins it) and stays what it was; ``inspect.signature(f, follow_wrapped=False)`` shows the option."""
+    (tests/test_gaps_host.py pins it) and stays what it was; ``inspect.signature(f, follow_wrapped=False)`` shows the option.
+    ``correct``: the step to run, with the signature of ``conserve`` (``rconserve.granule_option`` passes its own); default
+    ``conserve`` of this module."""
     sig = inspect.signature(fn)
+    correct = correct or globals()["conserve"]
 
     @functools.wraps(fn)
     def call(*args, conserve=0, **kw):
@@ -105,7 +108,7 @@ def granule_option(fn):
         a = a.arguments
         out, info = res if a.get("return_info") else (res, None)
         with torch.inference_mode():
-            out, stats = globals()["conserve"](out, a["lst_g"], a.get("mask"), n_iter=k, out=out, return_stats=True)
+            out, stats = correct(out, a["lst_g"], a.get("mask"), n_iter=k, out=out, return_stats=True)
         if info is None:
             return out
         info["conserve_stats"] = stats

@@ -16,8 +16,10 @@ multiple of 8 in 24..256 with window < hr <= 16 window; with p / q = hr / window
 is allowed and runs these kernels; the x4 functions of ``pipeline`` / ``predict`` / ``gaps`` keep theirs.  Everything is fp32 on the
 device; CPU tensors raise SifsrError: there is no CPU path.
 
-Fine-tuning on a granule at a ratio and masks in the loss at a ratio are ``sifsr.rloss``.  Out of scope here:
-``conserve=`` at a ratio, a captured ``GranulePredictor`` at a ratio, ``GraphedTrainStep`` at a ratio, mining patches at a ratio,
+Fine-tuning on a granule at a ratio and masks in the loss at a ratio are ``sifsr.rloss``; the consistency check
+and the residual correction at a ratio are ``sifsr.rconserve`` (§9 f20), which the two granule calls take as the keyword-only
+option ``conserve=k``.  Out of scope here:
+a captured ``GranulePredictor`` at a ratio, ``GraphedTrainStep`` at a ratio, mining patches at a ratio,
 ratios that are not ``hr / window`` for such a pair (926.25 / 90 and 231.656 / 90 stay with ``sifsr.degrade``), rerouting the
 drop-ins, and bf16."""
 from __future__ import annotations
@@ -28,6 +30,7 @@ from collections import namedtuple
 import torch
 
 from . import _granule, _lib, gaps
+from .rconserve import granule_option
 from .pipeline import _UNIT, _stats4, _tile_buffer
 
 Geometry = namedtuple("Geometry", "p q tiles hr_shape")
@@ -195,12 +198,16 @@ def blend_active_tiles(sr, slot, valid, window, hr, stats, overlap=0, cover_edge
     return out
 
 
+@granule_option
 @torch.inference_mode()
 def predict_granule(model, lst_g, ndvi_g, stats, window=64, hr=192, batch=256, overlap=0, cover_edges=False):
     """``predict.predict_granule`` at ratio ``hr / window``: raw LST raster (h,w) [K] + raw NDVI raster (h p/q, w p/q) ->
     super-resolved LST raster (h p/q, w p/q) [K].  Tiles are cut, normalised, resampled and concatenated by one kernel, pushed
     through the network in eval mode in batches of ``batch``, then de-normalised and blended by another; ``overlap`` (LST pixels,
-    a multiple of q, 0..window/2) and ``cover_edges`` are those of ``predict.predict_granule``."""
+    a multiple of q, 0..window/2) and ``cover_edges`` are those of ``predict.predict_granule``.
+
+    Keyword-only ``conserve=k`` (``rconserve.granule_option``): k steps of ``rconserve.conserve`` on the blended raster (cells of
+    0 K / non-finite LST pixels and the pixels no tile reached keep their bits); 0, the default: none."""
     _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
     lay = _tile_layout(lst_g, ndvi_g.shape, window, hr, overlap, cover_edges)                 # (raises before any launch)
     if int(batch) < 1:
@@ -209,6 +216,7 @@ def predict_granule(model, lst_g, ndvi_g, stats, window=64, hr=192, batch=256, o
     return _granule.predict(model, lay, lst_g, ndvi_g, stats, int(batch))
 
 
+@granule_option
 @torch.inference_mode()
 def predict_granule_gaps(model, lst_g, ndvi_g, stats, mask=None, window=64, hr=192, batch=256, overlap=16, cover_edges=True,
                          fill_value=float("nan"), return_info=False):
@@ -222,7 +230,11 @@ def predict_granule_gaps(model, lst_g, ndvi_g, stats, mask=None, window=64, hr=1
     pixels the result is bit-identical to ``predict_granule`` on the filled raster with the same layout; nothing valid: the
     all-``fill_value`` raster, no forward.
 
-    ``return_info``: also {"valid": bool (h,w) device tensor, "n_active": int, "n_tiles": int}."""
+    ``return_info``: also {"valid": bool (h,w) device tensor, "n_active": int, "n_tiles": int}.
+
+    Keyword-only ``conserve=k`` (``rconserve.granule_option``): k residual-correction steps on the blended raster
+    (``rconserve.conserve`` with the same ``mask``: only cells whose LST pixel is valid move, and the correction fades out towards
+    a gap); with ``return_info`` the statistics are ``info["conserve_stats"]``.  0, the default: none."""
     _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
     lay = _tile_layout(lst_g, ndvi_g.shape, window, hr, overlap, cover_edges)                 # (raises before any launch)
     if int(window) % 4:

@@ -12,7 +12,8 @@ Limits (``sifsrq_sif_loss``): 1 < factor <= 8, sides of ceil(factor) + 1 .. 1638
 default ceil(factor), at most 65535 images; ``sensor.sif_loss`` (composed, unmasked) serves what lies beyond them.  Everything is
 fp32 on the device; CPU tensors raise SifsrError: there is no CPU path.
 
-Out of scope here: ``GraphedTrainStep`` at a ratio (the call itself can be captured), ``conserve=`` at a ratio, a captured
+The consistency check and the residual correction at a ratio are ``sifsr.rconserve``.
+Out of scope here: ``GraphedTrainStep`` at a ratio (the call itself can be captured), a captured
 ``GranulePredictor`` at a ratio, mining patches at a ratio, the ``hkw`` argument in the loss, and bf16."""
 from __future__ import annotations
 
