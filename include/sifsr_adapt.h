@@ -49,6 +49,8 @@
  *               workspace is what sifsr_model_backward writes.
  *   dx          NULL, or (B, 2, H, W): the gradient with respect to x, by sifsra_conv_in_dgrad's kernel after the first layer's
  *               BatchNorm backward.  The SIFSR_HEAD_LINEAR switch counts as off in such a call.  `grads` does not depend on dx.
+ * Non-finite data (sifsr_hip.h): sifsra_model_forward gives NaN for every sr pixel of an image whose x is not finite and leaves the
+ * other images their bits; if d loss / d sr then holds a non-finite value, every element of `grads` and of dx is NaN.
  * Anything but 0 / 1 for `frozen`: 1002.  Null x / sr / dsr / params / running / grads / workspace: 1002. */
 SIFSR_API size_t sifsra_model_workspace_bytes(int B, int H, int W);
 SIFSR_API int sifsra_model_forward(const float* x, float* sr, const float* params, const float* running, void* workspace,

@@ -42,6 +42,29 @@ SIFSR_API size_t sifsr_model_workspace_bytes(int B, int H, int W, int training);
  * by its ReLU mask where the first layer's weight gradient runs in its linear form), dyB[3] (unused), gP[3], gU[3],
  * mean, invstd, scale, shift (per-channel vectors of all layers, indexed by ch_off).  Returns the count (56). */
 SIFSR_API int sifsr_model_workspace_regions(int B, int H, int W, size_t* out, int capacity);
+/* Non-finite data (NaN, +-inf in x, the parameters, the running statistics, lst, ndvi or a gradient) -- the model entry points
+ * (sifsr_model_forward / _backward, their _ex forms, sifsra_model_forward / _backward), sifsr_sif_loss, sifsr_huber_fwd / _bwd,
+ * sifsr_adam_flat / _dev, sifsr_psnr_ssim.  Rule, against the reference (PyTorch) run on the same input and on the input with the
+ * one bad element set to 0 ("repaired"): where the reference's output element is non-finite, so is the library's; where the
+ * library's is finite, it has the bits of its own result on the repaired input.  A superset is allowed:
+ *   - eval mode and frozen BatchNorm: every sr pixel of an image whose x holds a non-finite value is NaN (the reference: a box of
+ *     up to 140 x 140 pixels); the other images of the batch keep their bits;
+ *   - training mode: every sr pixel of the batch is NaN (the reference's behaviour: the batch statistics are poisoned);
+ *   - a non-finite parameter or running statistic, any mode: every sr pixel of the batch is NaN;
+ *   - backward: if the forward was poisoned or d loss / d sr holds a non-finite value, all 282,705 gradients are NaN (and dx, where
+ *     asked for); Adam then makes those elements of the parameters and of both moments non-finite and leaves the others alone;
+ *   - the losses: a NaN residual is a NaN loss value AND a NaN gradient there (nn.HuberLoss; the gradient's clamp is written with
+ *     comparisons), elsewhere the gradient is the usual clamp(e) / n; sifsr_psnr_ssim returns NaN for both values of a batch with a
+ *     NaN in either tensor, as skimage does.
+ * The model carries this beside the data: 1 + B + 1024 int flag words in the workspace (behind `shift`, inside
+ * sifsr_model_workspace_bytes, not a region of the table above), cleared by the first launch of every forward, raised by the kernels
+ * that read x, the parameters, the statistics and d loss / d sr anyway, consumed by the outlay kernel and the BatchNorm-backward
+ * finalizes; no launch, synchronisation or allocation is added, results on finite data keep their bits.  A backward inherits what
+ * its forward and any earlier backward on the same workspace found.
+ * NOT changed, on purpose: the staged-ReLU operators (sifsr_conv3x3_fwd* / _dgrad_fused / _wgrad_fused / _wgrad_wino / _bwd16*,
+ * sifsr_bnrelu_pool2 / _add / _up2x, sifsr_conv_out_fwd, sifsr_bn_relu_bwd*, the fused head and tail) called on their own keep
+ * relu(z) = max(z, 0) and the mask z > 0: a NaN pre-activation gives 0 there, not NaN -- one more packed instruction per ReLU in the
+ * MFMA staging would be paid by every step.  Out of scope: finite inputs that overflow inside the network; the exact footprint. */
 /* ModelB_2.forward, model.py:608-645.  training != 0: batch statistics, running-stat update
  * (momentum, unbiased var) and nbt += 1, activations kept in `workspace` for sifsr_model_backward;
  * training == 0: model.eval() semantics (running statistics), predict.py:68,100. */

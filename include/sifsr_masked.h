@@ -65,6 +65,8 @@ SIFSR_API int sifsrm_patches_fill(const float* lst, float* filled, unsigned char
  * target still constrains the prediction into the rim of a gap.  The high-frequency term is masked too: under a gap the network
  * input is the blocky fill, and texture trained on that input is not wanted.
  *   * lst[p] for p not in V is never read: a NaN there changes no output bit.
+ *   * a NaN residual at a VALID pixel (lst[p], or sr / ndvi under it) is a NaN loss value and a NaN gradient wherever that residual
+ *     reaches (sifsr_hip.h, "Non-finite data"); the other elements of dsr keep the bits of the call on the repaired input.
  *   * n <= 0: losses3 = {0, 0, 0} and dsr == 0 everywhere, no NaN.
  *   * every byte valid and n = B H W / 16: losses3 and dsr are bit-identical to sifsr_sif_loss on the same inputs (the weights and
  *     the finalisation scales are formed on the device by the IEEE double divisions and the one cast the host performs there).

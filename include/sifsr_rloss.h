@@ -33,7 +33,8 @@
  * n2 = B H W, bit for bit what an all-ones mask with its counts gives; exactly one of them NULL is 1002.  The blur and the low-pass
  * read sr and ndvi at EVERY pixel, so a valid target still constrains the prediction in the rim of a gap.  lst[p] for p outside V is
  * never read: a NaN there changes no output bit.  n1 <= 0 or n2 <= 0: losses3 = {0, 0, 0} and dsr = 0, no NaN.  An image without a
- * valid cell has dsr exactly 0.
+ * valid cell has dsr exactly 0.  A NaN residual at a VALID cell is a NaN loss value and a NaN gradient wherever the operators' supports
+ * carry it (sifsr_hip.h, "Non-finite data": clamp_d keeps a NaN); the other elements of dsr keep the bits of the repaired call.
  *
  * Arithmetic.  Weights, sums and residuals are float64.  By linearity dn = Ry sr Rx^T + (mean / std) (rowsum(Ry) rowsum(Rx) - 1):
  * nothing is rounded at the 300 K scale.  kind 2 applies ONE low-pass, e2 = (I - L)(sr - gamma ndvi), formed in float64.  The two

@@ -24,11 +24,18 @@ static __device__ __forceinline__ void block_sum2(double& s1, double& s2, double
   for (int w = 0; w < NT / 64; ++w) { s1 += wsum[w][0]; s2 += wsum[w][1]; }
 }
 
+// a * b + c * d with every operation rounded on its own (no contraction into an fma)
+static __device__ __forceinline__ float mul2_add(float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+  const float p = a * b, q = c * d;
+  return p + q;
+}
+
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ partials, int nblk, int C,
                                                           double count, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, float* run_mean,
                                                           float* run_var, float momentum, float eps, float* mean,
-                                                          float* invstd, float* scale, float* shift) {
+                                                          float* invstd, float* scale, float* shift, int* nf) {
   __shared__ double wsum[4][2];
   const int c = blockIdx.x, tid = threadIdx.x;
   double s1 = 0.0, s2 = 0.0;
@@ -46,12 +53,21 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
     mean[c] = (float)m;
     invstd[c] = istd;
     scale[c] = sc;
-    shift[c] = fmaf(-(float)m, sc, beta[c]);
+    const float sh = fmaf(-(float)m, sc, beta[c]);
+    shift[c] = sh;
+    // non-finite statistics, gamma or beta (common.h): the consumers' max(z, 0) would make 0 of them
+    bool bad = nonfinite(sc) || nonfinite(sh);
     if (run_mean != nullptr) {
       const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-      run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * (float)m;
-      run_var[c] = (1.f - momentum) * run_var[c] + momentum * (float)unb;
+      // (the roundings spelled out -- two products and a sum for the mean, one product and an fma for the variance: what the
+      // compiler made of `(1 - momentum) * r + momentum * v` before the values were also tested here, kept bit for bit)
+      const float rm = mul2_add(1.f - momentum, run_mean[c], momentum, (float)m);
+      const float rv = fmaf(momentum, (float)unb, (1.f - momentum) * run_var[c]);
+      run_mean[c] = rm;
+      run_var[c] = rv;
+      bad = bad || nonfinite(rm) || nonfinite(rv);
     }
+    if (nf != nullptr && bad) nf[NF_BATCH] = 1;
   }
 }
 
@@ -59,13 +75,22 @@ struct BnEvalTable { int gamma_off[SIFSR_NUM_BN_LAYERS], beta_off[SIFSR_NUM_BN_L
                          ch_off[SIFSR_NUM_BN_LAYERS], cout[SIFSR_NUM_BN_LAYERS]; };
 
 __global__ void bn_eval_coeffs_kernel(const float* __restrict__ params, const float* __restrict__ running, float eps,
-                                      float* scale, float* shift, const BnEvalTable tb) {
+                                      float* scale, float* shift, const BnEvalTable tb, int* nf,
+                                      const int* __restrict__ nf_pack) {
   const int l = blockIdx.x, c = threadIdx.x;
+  // (non-finite flags, common.h) the conv weights: the words the weight-pack launch before this one left, 64 per workgroup here
+  if (nf != nullptr) {
+    for (int i = l * 64 + c; i < NF_PACK_WORDS; i += SIFSR_NUM_BN_LAYERS * 64)
+      if (nf_pack[i] != 0) nf[NF_BATCH] = 1;
+  }
   if (c >= tb.cout[l]) return;
   const float rm = running[tb.run_off[l] + c], rv = running[tb.run_off[l] + tb.cout[l] + c];
   const float sc = params[tb.gamma_off[l] + c] / sqrtf(rv + eps);
+  const float sh = fmaf(-rm, sc, params[tb.beta_off[l] + c]);
   scale[tb.ch_off[l] + c] = sc;
-  shift[tb.ch_off[l] + c] = fmaf(-rm, sc, params[tb.beta_off[l] + c]);
+  shift[tb.ch_off[l] + c] = sh;
+  // ... and BatchNorm's own parameters and running statistics (a negative running_var included: sqrtf gives NaN)
+  if (nf != nullptr && (nonfinite(sc) || nonfinite(sh))) nf[NF_BATCH] = 1;
 }
 
 // Optional second gradient source: the AvgPool2d(2,2) adjoint of a half-resolution gradient gp, added on the fly,
@@ -171,6 +196,15 @@ static __device__ __forceinline__ void write_coef(double* coef, int C, int c, co
   }
 }
 
+// A call whose data is not finite (nf[NF_BATCH], common.h): NaN for this channel's gradients and for every coefficient, so that
+// whatever the consumers form from them -- dy = sc * dz + k1 * z + k0 whatever the ReLU mask says -- is NaN as well
+static __device__ __forceinline__ void poison_channel(float* dgamma, float* dbeta, double* coef, float* coef_f, int C, int c) {
+  const float nanf_ = __uint_as_float(0x7fc00000u);
+  dgamma[c] = nanf_; dbeta[c] = nanf_;
+  coef[c] = (double)nanf_; coef[C + c] = (double)nanf_; coef[2 * C + c] = (double)nanf_;
+  if (coef_f != nullptr) { coef_f[c] = nanf_; coef_f[C + c] = nanf_; coef_f[2 * C + c] = nanf_; coef_f[3 * C + c] = nanf_; }
+}
+
 // FROZEN (running-statistics BatchNorm, fine-tuning: DESIGN.md §9 f16): the statistics are constants of the backward, so dy = scale*dz --
 // k1 = k0 = 0 --, dbeta / dgamma keep their sums (the second sum carries the running mean / invstd the frozen forward left)
 template <bool FROZEN>
@@ -180,10 +214,12 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
                                                               const float* __restrict__ invstd, float* dgamma,
                                                               float* dbeta, double* coef, const float* __restrict__ shift,
                                                               const float* __restrict__ beta, float* coef_f,
-                                                              const float* __restrict__ xs_partials, int xs_n, float* __restrict__ xs_out) {
+                                                              const float* __restrict__ xs_partials, int xs_n, float* __restrict__ xs_out,
+                                                              const int* nf) {
   SIFSR_CHAIN_PRIO();
   __shared__ double wsum[4][2];
   const int c = blockIdx.x, tid = threadIdx.x;
+  const int poisoned = nf != nullptr ? nf[NF_BATCH] : 0;   // (read up front: its latency hides behind the partials)
   if (c >= C) {
     // rider (the tail of the backward): xs_out[e] = sum over the nblk rows of xs_partials[row][xs_n] -- the outlay weight / bias
     // gradient partials of the same pass; four outputs per extra workgroup, float64, fixed order (as sum_partials_kernel)
@@ -197,7 +233,7 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
     if (grp == 0 && e < xs_n) {
       double t = 0.0;
       for (int g = 0; g < 64; ++g) t += part[g][el];
-      xs_out[e] = (float)t;
+      xs_out[e] = poisoned != 0 ? __uint_as_float(0x7fc00000u) : (float)t;
     }
     return;
   }
@@ -215,6 +251,7 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
     // incoming gradient is smooth (ATen's CPU kernel also evaluates this in acc_type<float> = double)
     write_coef<FROZEN>(coef, C, c, scale, mean, invstd, db, dg, count);
     write_coef_f<FROZEN>(coef_f, C, c, scale, shift, invstd, beta, db, dg, count);
+    if (poisoned != 0) poison_channel(dgamma, dbeta, coef, coef_f, C, c);
   }
 }
 
@@ -227,10 +264,11 @@ __global__ __launch_bounds__(NT) void bn_bwd_finalize2_kernel(const float* __res
                                                                const float* __restrict__ mean,
                                                                const float* __restrict__ invstd, float* dgamma,
                                                                float* dbeta, double* coef, const float* __restrict__ shift,
-                                                               const float* __restrict__ beta, float* coef_f) {
+                                                               const float* __restrict__ beta, float* coef_f, const int* nf) {
   SIFSR_CHAIN_PRIO();
   __shared__ double wsum[NT / 64][2];
   const int c = blockIdx.x, tid = threadIdx.x;
+  const int poisoned = nf != nullptr ? nf[NF_BATCH] : 0;   // (read up front: its latency hides behind the partials)
   double s1 = 0.0, s2 = 0.0;
   for (int k = tid; k < na; k += NT) { const float2 v = *reinterpret_cast<const float2*>(pa + ((size_t)k * C + c) * 2); s1 += (double)v.x; s2 += (double)v.y; }
   for (int k = tid; k < nb; k += NT) { const float2 v = *reinterpret_cast<const float2*>(pb + ((size_t)k * C + c) * 2); s1 += (double)v.x; s2 += (double)v.y; }
@@ -242,6 +280,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_finalize2_kernel(const float* __res
     dgamma[c] = (float)dg;
     write_coef<FROZEN>(coef, C, c, scale, mean, invstd, db, dg, count);
     write_coef_f<FROZEN>(coef_f, C, c, scale, shift, invstd, beta, db, dg, count);
+    if (poisoned != 0) poison_channel(dgamma, dbeta, coef, coef_f, C, c);
   }
 }
 
@@ -280,21 +319,23 @@ __global__ void nbt_increment_kernel(long long* nbt, int n) {
 
 int launch_bn_finalize(const float* partials, int nblk, int C, double count, const float* gamma, const float* beta,
                        float* run_mean, float* run_var, float momentum, float eps, float* mean, float* invstd,
-                       float* scale, float* shift, hipStream_t s) {
+                       float* scale, float* shift, hipStream_t s, int* nf) {
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, s, partials, nblk, C, count, gamma, beta, run_mean,
-                     run_var, momentum, eps, mean, invstd, scale, shift);
+                     run_var, momentum, eps, mean, invstd, scale, shift, nf);
   SIFSR_LAUNCH_CHECK();
   return SIFSR_OK;
 }
 
-int launch_bn_eval_coeffs(const float* params, const float* running, float eps, float* scale, float* shift, hipStream_t s) {
+int launch_bn_eval_coeffs(const float* params, const float* running, float eps, float* scale, float* shift, hipStream_t s, int* nf,
+                          const int* nf_pack) {
+  if ((nf == nullptr) != (nf_pack == nullptr)) return SIFSR_ERR_ARG;
   const NetTable& nt = sifsr_net();
   BnEvalTable tb;
   for (int l = 0; l < SIFSR_NUM_BN_LAYERS; ++l) {
     tb.gamma_off[l] = nt.L[l].gamma_off; tb.beta_off[l] = nt.L[l].beta_off; tb.run_off[l] = nt.L[l].run_off;
     tb.ch_off[l] = nt.L[l].ch_off; tb.cout[l] = nt.L[l].cout;
   }
-  hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3(SIFSR_NUM_BN_LAYERS), dim3(64), 0, s, params, running, eps, scale, shift, tb);
+  hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3(SIFSR_NUM_BN_LAYERS), dim3(64), 0, s, params, running, eps, scale, shift, tb, nf, nf_pack);
   SIFSR_LAUNCH_CHECK();
   return SIFSR_OK;
 }
@@ -327,27 +368,28 @@ int launch_bn_bwd_reduce(const float* g, const float* y, const float* scale, con
 
 int launch_bn_bwd_finalize(const float* partials, int nblk, int C, double count, const float* scale, const float* mean,
                            const float* invstd, float* dgamma, float* dbeta, double* coef, hipStream_t s, const float* shift,
-                           const float* beta, float* coef_f, const float* xs_partials, int xs_n, float* xs_out, int frozen) {
+                           const float* beta, float* coef_f, const float* xs_partials, int xs_n, float* xs_out, int frozen,
+                           const int* nf) {
   if (coef_f != nullptr && (!shift || !beta)) return SIFSR_ERR_ARG;
   if (xs_partials != nullptr && (xs_n < 1 || !xs_out)) return SIFSR_ERR_ARG;
   const int extra = xs_partials != nullptr ? (xs_n + 3) / 4 : 0;
   if (frozen)
     hipLaunchKernelGGL(bn_bwd_finalize_kernel<true>, dim3(C + extra), dim3(256), 0, s, partials, nblk, C, count, scale, mean, invstd,
-                       dgamma, dbeta, coef, shift, beta, coef_f, xs_partials, xs_n, xs_out);
+                       dgamma, dbeta, coef, shift, beta, coef_f, xs_partials, xs_n, xs_out, nf);
   else
     hipLaunchKernelGGL(bn_bwd_finalize_kernel<false>, dim3(C + extra), dim3(256), 0, s, partials, nblk, C, count, scale, mean, invstd,
-                       dgamma, dbeta, coef, shift, beta, coef_f, xs_partials, xs_n, xs_out);
+                       dgamma, dbeta, coef, shift, beta, coef_f, xs_partials, xs_n, xs_out, nf);
   SIFSR_LAUNCH_CHECK();
   return SIFSR_OK;
 }
 
 int launch_bn_bwd_finalize2(const float* pa, int na, const float* pb, int nb, int C, double count, const float* scale,
                             const float* mean, const float* invstd, float* dgamma, float* dbeta, double* coef, hipStream_t s,
-                            const float* shift, const float* beta, float* coef_f, int frozen) {
+                            const float* shift, const float* beta, float* coef_f, int frozen, const int* nf) {
   if (coef_f != nullptr && (!shift || !beta)) return SIFSR_ERR_ARG;
   // NOTE: the result depends on the thread count (summation order), so the choice is a function of the row count alone
 #define BN_FIN2(NT_, FR_) hipLaunchKernelGGL((bn_bwd_finalize2_kernel<NT_, FR_>), dim3(C), dim3(NT_), 0, s, pa, na, pb, nb, C, count, scale, mean, \
-                                             invstd, dgamma, dbeta, coef, shift, beta, coef_f)
+                                             invstd, dgamma, dbeta, coef, shift, beta, coef_f, nf)
   if (na + nb > 4096) { if (frozen) BN_FIN2(1024, true); else BN_FIN2(1024, false); }
   else { if (frozen) BN_FIN2(256, true); else BN_FIN2(256, false); }
 #undef BN_FIN2

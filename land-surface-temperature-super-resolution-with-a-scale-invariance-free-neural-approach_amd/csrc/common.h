@@ -139,6 +139,21 @@ static __device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {   // same rea
 }
 #endif
 
+// ---- non-finite data (include/sifsr_hip.h, "Non-finite data") ----
+// bn_relu4 above is fma then MAX and bn_bwd4 below masks with `z > 0`: both turn a NaN into 0, and both stay that way -- one
+// more packed instruction per ReLU inside the MFMA staging is paid by every step.  The model carries the poison beside the data
+// instead, in int words of the workspace (WsLayout::nf) that kernels which read or write the data anyway set and consume:
+//   nf[NF_BATCH]              the whole call: a non-finite parameter or running statistic (pack_all_kernel's words below, read by
+//                             bn_eval_coeffs_kernel; bn_finalize_kernel), non-finite batch statistics (bn_finalize_kernel), a
+//                             non-finite d loss / d sr (tail_bwd_reduce_kernel)
+//   nf[NF_IMAGE + b]          image b: conv_in_fwd_kernel produced a non-finite value from x[b] or its own weights
+//   nf[NF_IMAGE + B + i]      weight-pack workgroup i saw a non-finite conv weight: written by EVERY such workgroup, 0 or 1
+// pack_all_kernel, the first launch of every forward, clears the first 1 + B words; every later writer stores the one value 1
+// (plain stores, no atomics); conv_out_fwd_kernel writes NaN for a flagged image, the BatchNorm-backward finalizes NaN
+// coefficients and gradients for a flagged call.  Nothing reads a word that the same call did not write.
+enum { NF_BATCH = 0, NF_IMAGE = 1, NF_PACK_WORDS = 64 * 16 };
+static __device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
 // BatchNorm + ReLU BACKWARD applied while a consumer stages its operand (the input-gradient and weight-gradient
 // convolutions of layer l read g_l = dL/d relu(bn(y_l)) and y_l instead of a stored dL/dy_l):
 //   z  = fma(y, sc, sh)                      the forward's pre-activation, bit for bit (same fma) -> same ReLU mask

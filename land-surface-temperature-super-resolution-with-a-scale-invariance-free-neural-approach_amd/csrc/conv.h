@@ -160,4 +160,7 @@ int dgrad_border_waves(int B, int H, int W, int Cin);   // rows of bn_partials (
 // wwf / wwd (optional): Winograd-domain packs of all layers, 16/9 of the size and offsets of wfwd
 // nbt (optional, with the Winograd packs): nbt_n int64 counters incremented by the same launch (BatchNorm num_batches_tracked)
 int launch_pack_weights(const float* params, float* wfwd, float* wdgrad, hipStream_t s, float* wwf = nullptr, float* wwd = nullptr,
-                        long long* nbt = nullptr, int nbt_n = 0);
+                        long long* nbt = nullptr, int nbt_n = 0,
+                        // nf (optional, with the Winograd packs): the non-finite flag words (common.h); the launch clears the first
+                        // nf_clear and writes NF_PACK_WORDS behind them, one per tap-pack workgroup
+                        int* nf = nullptr, int nf_clear = 0);

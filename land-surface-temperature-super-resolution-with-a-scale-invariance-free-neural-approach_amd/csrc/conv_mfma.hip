@@ -754,12 +754,14 @@ __global__ __launch_bounds__(512, (WINO ? (NB == 1 && !ZERO_PAD ? 4 : 2) : (NB <
 // ---------------------------------------------------------------------------------------------
 struct PackTable { int w_off[16], cin[16], cout[16], p_off[16]; };
 
-static __device__ __forceinline__ void pack_weights_body(const float* __restrict__ params, float* __restrict__ wfwd,
+// Returns whether this thread read a non-finite weight (the forward pack reads every weight of the layer exactly once).
+static __device__ __forceinline__ bool pack_weights_body(const float* __restrict__ params, float* __restrict__ wfwd,
                                                          float* __restrict__ wdg, const PackTable& tb, int bx, int gdx) {
   const int l = blockIdx.y;
   const int cin = tb.cin[l], cout = tb.cout[l];
   const int n = 9 * cin * cout;
   const float* W = params + tb.w_off[l];
+  bool bad = false;
   for (int e = bx * blockDim.x + threadIdx.x; e < n; e += gdx * blockDim.x) {
     const int j = e & 3, lane = (e >> 2) & 63;
     const int rest = e >> 8;
@@ -768,7 +770,9 @@ static __device__ __forceinline__ void pack_weights_body(const float* __restrict
       const int NQ = cin / 16;
       const int q = r2 % NQ, nb = r2 / NQ;
       const int co = 16 * nb + (lane & 15), ci = 16 * q + 4 * (lane >> 4) + j;
-      wfwd[tb.p_off[l] + e] = W[(co * cin + ci) * 9 + tap];
+      const float wv = W[(co * cin + ci) * 9 + tap];
+      wfwd[tb.p_off[l] + e] = wv;
+      bad = bad || nonfinite(wv);
     }
     {
       const int NQ = cout / 16;
@@ -787,6 +791,7 @@ static __device__ __forceinline__ void pack_weights_body(const float* __restrict
       }
     }
   }
+  return bad;
 }
 
 // Winograd-domain weights U = G g G^T (4x4 per (cout, cin) pair; G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]) in
@@ -794,7 +799,7 @@ static __device__ __forceinline__ void pack_weights_body(const float* __restrict
 //   ww[nb][q][xi][lane][j], xi = 4a + b, same (lane, j) -> (row, k) map as the tap packs above; 16*cin*cout floats each.
 __global__ void pack_weights_kernel(const float* __restrict__ params, float* __restrict__ wfwd,
                                     float* __restrict__ wdg, const PackTable tb) {
-  pack_weights_body(params, wfwd, wdg, tb, blockIdx.x, gridDim.x);
+  (void)pack_weights_body(params, wfwd, wdg, tb, blockIdx.x, gridDim.x);
 }
 
 static __device__ __forceinline__ void pack_wino_body(const float* __restrict__ params, float* __restrict__ wwf,
@@ -836,9 +841,18 @@ __global__ void pack_wino_kernel(const float* __restrict__ params, float* __rest
 // all four packs of all layers (+ the BatchNorm num_batches_tracked counters of a training-mode forward) in ONE launch: the three
 // launches this replaces were 20 us at the head of every forward for < 2 us of work.  blockIdx.x < gx: tap packs; the rest: Winograd.
 __global__ void pack_all_kernel(const float* __restrict__ params, float* __restrict__ wfwd, float* __restrict__ wdg,
-                                float* __restrict__ wwf, float* __restrict__ wwd, const PackTable tb, int gx, long long* nbt, int nbt_n) {
-  if ((int)blockIdx.x < gx) pack_weights_body(params, wfwd, wdg, tb, blockIdx.x, gx);
-  else pack_wino_body(params, wwf, wwd, tb, (int)blockIdx.x - gx, (int)gridDim.x - gx);
+                                float* __restrict__ wwf, float* __restrict__ wwd, const PackTable tb, int gx, long long* nbt, int nbt_n,
+                                int* __restrict__ nf, int nf_clear) {
+  // non-finite flags (common.h): as the first launch of a forward this kernel clears the words that LATER launches raise, and every
+  // tap-pack workgroup reports its own weights in a word of its own (written whatever it found: nothing is left over from before)
+  if (nf != nullptr && blockIdx.x == 0 && blockIdx.y == 0)
+    for (int i = threadIdx.x; i < nf_clear; i += blockDim.x) nf[i] = 0;
+  if ((int)blockIdx.x < gx) {
+    const int bad = __syncthreads_or(pack_weights_body(params, wfwd, wdg, tb, blockIdx.x, gx) ? 1 : 0);
+    if (nf != nullptr && threadIdx.x == 0) nf[nf_clear + blockIdx.y * gx + blockIdx.x] = bad ? 1 : 0;
+  } else {
+    pack_wino_body(params, wwf, wwd, tb, (int)blockIdx.x - gx, (int)gridDim.x - gx);
+  }
   if (nbt != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && (int)threadIdx.x < nbt_n) nbt[threadIdx.x] += 1;
 }
 
@@ -1194,7 +1208,8 @@ int launch_conv3x3_mfma(const ConvArgs& a, int cout, int zero_pad, hipStream_t s
   return SIFSR_OK;
 }
 
-int launch_pack_weights(const float* params, float* wfwd, float* wdgrad, hipStream_t s, float* wwf, float* wwd, long long* nbt, int nbt_n) {
+int launch_pack_weights(const float* params, float* wfwd, float* wdgrad, hipStream_t s, float* wwf, float* wwd, long long* nbt, int nbt_n,
+                        int* nf, int nf_clear) {
   const NetTable& nt = sifsr_net();
   PackTable tb;
   int maxn = 0;
@@ -1209,9 +1224,11 @@ int launch_pack_weights(const float* params, float* wfwd, float* wdgrad, hipStre
   const dim3 grid((maxn + 255) / 256 > 64 ? 64 : (maxn + 255) / 256, 16);
   if (nbt != nullptr && (nbt_n < 1 || nbt_n > 256)) return SIFSR_ERR_ARG;
   if (wwf != nullptr && wwd != nullptr) {
-    hipLaunchKernelGGL(pack_all_kernel, dim3(grid.x * 3, 16), dim3(256), 0, s, params, wfwd, wdgrad, wwf, wwd, tb, (int)grid.x, nbt, nbt_n);
+    if (nf != nullptr && (nf_clear < 1 || (int)grid.x * 16 != NF_PACK_WORDS)) return SIFSR_ERR_ARG;   // (the reader takes all of them)
+    hipLaunchKernelGGL(pack_all_kernel, dim3(grid.x * 3, 16), dim3(256), 0, s, params, wfwd, wdgrad, wwf, wwd, tb, (int)grid.x, nbt, nbt_n,
+                       nf, nf_clear);
   } else {
-    if (nbt != nullptr) return SIFSR_ERR_ARG;
+    if (nbt != nullptr || nf != nullptr) return SIFSR_ERR_ARG;
     hipLaunchKernelGGL(pack_weights_kernel, grid, dim3(256), 0, s, params, wfwd, wdgrad, tb);
   }
   SIFSR_LAUNCH_CHECK();

@@ -5,10 +5,13 @@
 
 // ---- edge_conv.hip ----
 int conv_in_fwd_blocks(int B, int H, int W);   // rows of `partials` ([blocks][16][2]) launch_conv_in_fwd writes
-int launch_conv_in_fwd(const float* x, const float* w, float* y, float* partials, int B, int H, int W, hipStream_t s);
+// nf_image (optional): the per-image non-finite flag words (common.h NF_IMAGE), raised for an image whose output is not finite
+int launch_conv_in_fwd(const float* x, const float* w, float* y, float* partials, int B, int H, int W, hipStream_t s,
+                       int* nf_image = nullptr);
 int launch_conv_in_wgrad(const float* x, const float* dy, float* partials, int nblk, float* dw, int B, int H, int W, hipStream_t s);
 int launch_conv_out_fwd(const float* y, const float* scale, const float* shift, const float* w, const float* bias,
-                        float* out, int B, int H, int W, hipStream_t s);
+                        float* out, int B, int H, int W, hipStream_t s,
+                        const int* nf = nullptr);   // nf (optional): the flag words; NaN for image b if nf[NF_BATCH] or nf[NF_IMAGE + b]
 int launch_conv_out_dgrad(const float* dsr, const float* w, float* g, int B, int H, int W, hipStream_t s);
 int launch_conv_out_wgrad(const float* y, const float* scale, const float* shift, const float* dsr, float* partials,
                           int nblk, float* dw, float* db, int B, int H, int W, hipStream_t s);
@@ -24,7 +27,7 @@ int launch_conv_in_dw_combine(const float* partials, int nblk, const double* gra
 // ---- fused_edges.hip ---- (outlay backward + BatchNorm/ReLU backward of its producer)
 int launch_tail_bwd_reduce(const float* y, const float* scale, const float* shift, const float* mean, const float* invstd,
                            const float* dsr, const float* w, float* wpart, float* bnpart, int nblk, int B, int H, int W,
-                           hipStream_t s);
+                           hipStream_t s, int* nf = nullptr);   // nf (optional): nf[NF_BATCH] raised when d loss / d sr is not finite
 int launch_tail_bwd_apply(const float* y, const float* scale, const float* shift, const double* coef, const float* dsr,
                           const float* w, float* dy, int B, int H, int W, hipStream_t s);
 int launch_sum_partials(const float* partials, int nblk, int n, float* out, hipStream_t s);
@@ -33,9 +36,13 @@ int launch_sum_partials(const float* partials, int nblk, int n, float* out, hipS
 // training: per-workgroup (sum, sumsq) partials -> batch mean / invstd, folded scale/shift, running-stat update
 int launch_bn_finalize(const float* partials, int nblk, int C, double count, const float* gamma, const float* beta,
                        float* run_mean, float* run_var, float momentum, float eps, float* mean, float* invstd,
-                       float* scale, float* shift, hipStream_t s);
+                       float* scale, float* shift, hipStream_t s,
+                       int* nf = nullptr);   // nf (optional): nf[NF_BATCH] raised for non-finite scale / shift / running statistics
 // eval: scale/shift from the running statistics of all 17 layers in one launch
-int launch_bn_eval_coeffs(const float* params, const float* running, float eps, float* scale, float* shift, hipStream_t s);
+// nf / nf_pack (optional, both or neither): nf[NF_BATCH] raised for non-finite coefficients and for a set word of the weight-pack
+// launch's NF_PACK_WORDS at nf_pack
+int launch_bn_eval_coeffs(const float* params, const float* running, float eps, float* scale, float* shift, hipStream_t s,
+                          int* nf = nullptr, const int* nf_pack = nullptr);
 // gp != nullptr: the AvgPool2d(2,2) adjoint of the half-resolution gradient gp (image H x W at full resolution) is
 // added to g on the fly in both passes:  g_eff = g + 0.25 * gp[y/2][x/2]
 // g_out (== g, only with gp): the completed gradient g_eff is also written back in place, for consumers that form
@@ -50,10 +57,12 @@ int launch_bn_bwd_finalize(const float* partials, int nblk, int C, double count,
                            const float* shift = nullptr, const float* beta = nullptr, float* coef_f = nullptr,
                            const float* xs_partials = nullptr, int xs_n = 0, float* xs_out = nullptr,   // xs_*: a rider, xs_out[e] =
                            // the column sums of xs_partials[nblk][xs_n] (same row count) -- one launch less on the chain
-                           int frozen = 0);   // frozen (both finalizes): running-statistics BatchNorm, k1 = k0 = 0
+                           int frozen = 0,    // frozen (both finalizes): running-statistics BatchNorm, k1 = k0 = 0
+                           const int* nf = nullptr);   // nf (both finalizes): NaN gradients and coefficients when nf[NF_BATCH] is set
 int launch_bn_bwd_finalize2(const float* pa, int na, const float* pb, int nb, int C, double count, const float* scale,
                             const float* mean, const float* invstd, float* dgamma, float* dbeta, double* coef, hipStream_t s,
-                            const float* shift = nullptr, const float* beta = nullptr, float* coef_f = nullptr, int frozen = 0);
+                            const float* shift = nullptr, const float* beta = nullptr, float* coef_f = nullptr, int frozen = 0,
+                            const int* nf = nullptr);
 int launch_bn_bwd_apply(const float* g, const float* y, const float* scale, const float* shift, const double* coef,
                         int C, size_t npix, float* dy, hipStream_t s, const float* gp = nullptr, int H = 0, int W = 0);
 int launch_nbt_increment(long long* nbt, int n, hipStream_t s);

@@ -18,7 +18,7 @@ namespace {
 template <bool HS>   // HS: y stored as bf16 (the bf16 compute mode, common.h); the statistics are those of the stored values
 __global__ __launch_bounds__(256) void conv_in_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                           float* __restrict__ y, float* __restrict__ partials,
-                                                          int B, int H, int W) {
+                                                          int B, int H, int W, int* __restrict__ nf_image) {
   // PERSISTENT since round 3: conv_in_fwd_blocks() workgroups walk the 16x16 tiles, so the BatchNorm statistics come out as
   // <= 2048 partial rows instead of one per tile (16,384 at batch 64: the finalize launch behind it took 28 us, now 7)
   __shared__ float tile[2][2 * 324];
@@ -54,6 +54,7 @@ __global__ __launch_bounds__(256) void conv_in_fwd_kernel(const float* __restric
     const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
     const int x0 = tx * 16, y0 = ty * 16;
     const float* T = tile[buf];
+    bool bad = false;                                  // a non-finite output in this tile: from x[b] or from w (common.h)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = 4 * wave + r;
@@ -66,9 +67,10 @@ __global__ __launch_bounds__(256) void conv_in_fwd_kernel(const float* __restric
         stA4<HS>(y, ((size_t)(b * H + y0 + row) * W + x0 + i) * 16 + 4 * kq, o);
         const float ov[4] = {o.x, o.y, o.z, o.w};
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { s1[q] += ov[q]; s2[q] = fmaf(ov[q], ov[q], s2[q]); }
+        for (int q = 0; q < 4; ++q) { s1[q] += ov[q]; s2[q] = fmaf(ov[q], ov[q], s2[q]); bad = bad || nonfinite(ov[q]); }
       }
     }
+    if (nf_image != nullptr && bad) nf_image[b] = 1;
   }
   if (partials != nullptr) {
 #pragma unroll
@@ -190,12 +192,14 @@ template <bool HS>
 __global__ __launch_bounds__(256) void conv_out_fwd_kernel(const float* __restrict__ y, const float* scale,
                                                            const float* shift, const float* __restrict__ w,
                                                            const float* __restrict__ bias, float* __restrict__ out,
-                                                           int H, int W) {
+                                                           int H, int W, const int* __restrict__ nf) {
   constexpr int NGRP = 21;                      // ceil(324 / 16) groups of 16 halo pixels
   __shared__ float P[NGRP * 16 * 9];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i = lane & 15, kq = lane >> 4;
   const int x0 = blockIdx.x * 16, y0 = blockIdx.y * 16, b = blockIdx.z;
+  // non-finite data upstream (common.h): the ReLUs on the way made zeros of it, the flags say so (read up front, used at the end)
+  const int poisoned = nf != nullptr ? (nf[NF_BATCH] | nf[NF_IMAGE + b]) : 0;
   float wb[4];                                   // B[k = kq][n = tap i] of MFMA j: w is (1,16,3,3) = [ci][t]
 #pragma unroll
   for (int j = 0; j < 4; ++j) wb[j] = i < 9 ? w[(4 * kq + j) * 9 + i] : 0.f;
@@ -233,6 +237,7 @@ __global__ __launch_bounds__(256) void conv_out_fwd_kernel(const float* __restri
   float s = bias[0];
 #pragma unroll
   for (int t = 0; t < 9; ++t) s += P[((ty + t / 3) * 18 + tx + t % 3) * 9 + t];
+  if (poisoned != 0) s = __uint_as_float(0x7fc00000u);
   if (y0 + ty < H && x0 + tx < W) out[(size_t)(b * H + y0 + ty) * W + x0 + tx] = s;
 }
 
@@ -597,10 +602,10 @@ int conv_in_fwd_blocks(int B, int H, int W) {   // workgroups launched == statis
   return ntiles < 2048 ? ntiles : 2048;
 }
 
-int launch_conv_in_fwd(const float* x, const float* w, float* y, float* partials, int B, int H, int W, hipStream_t s) {
+int launch_conv_in_fwd(const float* x, const float* w, float* y, float* partials, int B, int H, int W, hipStream_t s, int* nf_image) {
   if (H < 1 || W < 1 || B < 1) return SIFSR_ERR_SHAPE;
-  if (sifsr_half_storage()) hipLaunchKernelGGL(conv_in_fwd_kernel<true>, dim3(conv_in_fwd_blocks(B, H, W)), dim3(256), 0, s, x, w, y, partials, B, H, W);
-  else hipLaunchKernelGGL(conv_in_fwd_kernel<false>, dim3(conv_in_fwd_blocks(B, H, W)), dim3(256), 0, s, x, w, y, partials, B, H, W);
+  if (sifsr_half_storage()) hipLaunchKernelGGL(conv_in_fwd_kernel<true>, dim3(conv_in_fwd_blocks(B, H, W)), dim3(256), 0, s, x, w, y, partials, B, H, W, nf_image);
+  else hipLaunchKernelGGL(conv_in_fwd_kernel<false>, dim3(conv_in_fwd_blocks(B, H, W)), dim3(256), 0, s, x, w, y, partials, B, H, W, nf_image);
   SIFSR_LAUNCH_CHECK();
   return SIFSR_OK;
 }
@@ -656,10 +661,10 @@ int launch_conv_in_dw_combine(const float* partials, int nblk, const double* gra
 }
 
 int launch_conv_out_fwd(const float* y, const float* scale, const float* shift, const float* w, const float* bias,
-                        float* out, int B, int H, int W, hipStream_t s) {
+                        float* out, int B, int H, int W, hipStream_t s, const int* nf) {
   if (H < 1 || W < 1) return SIFSR_ERR_SHAPE;
-  if (sifsr_half_storage()) hipLaunchKernelGGL(conv_out_fwd_kernel<true>, dim3((W + 15) / 16, (H + 15) / 16, B), dim3(256), 0, s, y, scale, shift, w, bias, out, H, W);
-  else hipLaunchKernelGGL(conv_out_fwd_kernel<false>, dim3((W + 15) / 16, (H + 15) / 16, B), dim3(256), 0, s, y, scale, shift, w, bias, out, H, W);
+  if (sifsr_half_storage()) hipLaunchKernelGGL(conv_out_fwd_kernel<true>, dim3((W + 15) / 16, (H + 15) / 16, B), dim3(256), 0, s, y, scale, shift, w, bias, out, H, W, nf);
+  else hipLaunchKernelGGL(conv_out_fwd_kernel<false>, dim3((W + 15) / 16, (H + 15) / 16, B), dim3(256), 0, s, y, scale, shift, w, bias, out, H, W, nf);
   SIFSR_LAUNCH_CHECK();
   return SIFSR_OK;
 }

@@ -9,6 +9,7 @@
 struct WsLayout {
   size_t npix[4];                         // B*H*W at the four resolution levels
   size_t mean, invstd, scale, shift;      // per-channel vectors, all 17 BN layers back to back
+  size_t nf;                              // non-finite flags (int words, common.h NF_*): [batch | image 0..B-1 | one per weight-pack workgroup]
   size_t wfwd, wdg;                       // fragment-ordered conv weights (forward / dgrad)
   size_t wwf, wwd;                        // the same in the Winograd F(2x2,3x3) domain (16 instead of 9 values per weight pair)
   size_t y[SIFSR_NUM_BN_LAYERS];          // raw conv outputs (pre-BN), NHWC

@@ -112,6 +112,8 @@ int sifsr_layout(int B, int H, int W, int training, WsLayout* o) {
 
   w.mean = take(nt.total_channels); w.invstd = take(nt.total_channels);
   w.scale = take(nt.total_channels); w.shift = take(nt.total_channels);
+  // (in front of the activations, not beside the statistic partials: it lives from the forward's first launch to the backward's last)
+  w.nf = take(NF_IMAGE + (size_t)B + NF_PACK_WORDS);
   w.wfwd = take(nt.total_wpack); w.wdg = take(4 * (size_t)nt.total_wpack);
   w.wwf = take((size_t)nt.total_wpack / 9 * 16); w.wwd = take((size_t)nt.total_wpack / 9 * 16);   // Winograd-domain packs
   for (int l = 0; l < SIFSR_NUM_BN_LAYERS; ++l) w.y[l] = take(nt.L[l].cout * N[nt.L[l].level]);
@@ -202,6 +204,7 @@ struct Ctx {
   float* coef_f(int l) const { return ws + lay.coef_f + 4 * (size_t)nt.L[l].ch_off; }        // bn_bwd4's [sc | sh | k1 | k0]
   double* coef() const { return reinterpret_cast<double*>(ws + lay.coef); }                  // ... of the current layer, float64
   float* slab(int l) const { return ws + lay.slab_l[l]; }
+  int* nf() const { return reinterpret_cast<int*>(ws + lay.nf); }                           // the non-finite flag words (common.h)
   // weight packs of layer l.  Its part of the wdg region is [fp32 dgrad | fwd bf16 (n / 2 floats) | dgrad bf16 | unused], n = 9 * cin * cout
   size_t wn(int l) const { return (size_t)9 * nt.L[l].cin * nt.L[l].cout; }
   const float* w_dgrad_f32(int l) const { return ws + lay.wdg + 4 * (size_t)nt.L[l].wpack_off; }
@@ -348,7 +351,7 @@ int bn_unit_finalize(const Ctx& c, int l, int nblk, float* running, float moment
   const LayerInfo& L = c.nt.L[l];
   return launch_bn_finalize(c.f(c.lay.partials), nblk, L.cout, (double)c.lay.npix[L.level], c.params + L.gamma_off,
                             c.params + L.beta_off, running + L.run_off, running + L.run_off + L.cout, momentum, eps,
-                            c.mean(l), c.invstd(l), c.scale(l), c.shift(l), c.s);
+                            c.mean(l), c.invstd(l), c.scale(l), c.shift(l), c.s, c.nf());
 }
 
 // forward of one MFMA Conv(-BN) unit
@@ -397,13 +400,13 @@ int bn_unit_bwd(const Ctx& c, int l, const float* gp = nullptr, int fused_stats 
     if (gp != nullptr) return SIFSR_ERR_ARG;
     return launch_bn_bwd_finalize2(c.f(c.lay.partials), fused_stats, c.f(c.lay.bpart), border_rows >= 0 ? border_rows : dgrad_border_waves(c.B, lh, lw, 16),
                                    L.cout, (double)npix, c.scale(l), c.mean(l), c.invstd(l), dgamma, dbeta, c.coef(), c.s, c.shift(l),
-                                   c.params + L.beta_off, c.coef_f(l), c.frozen);
+                                   c.params + L.beta_off, c.coef_f(l), c.frozen, c.nf());
   }
   const int nblk = bn_bwd_reduce_blocks(npix);
   SIFSR_TRY(launch_bn_bwd_reduce(c.g(l), c.y(l), c.scale(l), c.shift(l), c.mean(l), c.invstd(l), L.cout, npix, c.f(c.lay.partials), nblk,
                                  c.s, gp, lh, lw, (gp && writeback) ? c.g(l) : nullptr));
   return launch_bn_bwd_finalize(c.f(c.lay.partials), nblk, L.cout, (double)npix, c.scale(l), c.mean(l), c.invstd(l), dgamma, dbeta,
-                                c.coef(), c.s, c.shift(l), c.params + L.beta_off, c.coef_f(l), nullptr, 0, nullptr, c.frozen);
+                                c.coef(), c.s, c.shift(l), c.params + L.beta_off, c.coef_f(l), nullptr, 0, nullptr, c.frozen, c.nf());
 }
 
 // SIFSR_WGRAD_WINO (switches.h): the Winograd-domain weight-gradient kernels for a layer with cout output channels?
@@ -603,13 +606,15 @@ int sifsr_engine_forward(const float* x, float* sr, const float* params, float* 
   const NetTable& nt = c.nt;
   const WsLayout& w = c.lay;
 
-  SIFSR_TRY(launch_pack_weights(params, c.f(w.wfwd), c.f(w.wdg), s, c.f(w.wwf), c.f(w.wwd), training ? nbt : nullptr, SIFSR_NUM_BN_LAYERS));
+  SIFSR_TRY(launch_pack_weights(params, c.f(w.wfwd), c.f(w.wdg), s, c.f(w.wwf), c.f(w.wwd), training ? nbt : nullptr, SIFSR_NUM_BN_LAYERS,
+                                c.nf(), NF_IMAGE + B));
   if (!training) {
-    SIFSR_TRY(launch_bn_eval_coeffs(params, running, eps, c.f(w.scale), c.f(w.shift), s));
+    SIFSR_TRY(launch_bn_eval_coeffs(params, running, eps, c.f(w.scale), c.f(w.shift), s, c.nf(), c.nf() + NF_IMAGE + B));
   }
 
   // inbloc (DoubleConvolution, model.py:596)
-  SIFSR_TRY(launch_conv_in_fwd(x, params + nt.L[L_IN0].w_off, c.y(L_IN0), training ? c.f(w.partials) : nullptr, B, H, W, s));
+  SIFSR_TRY(launch_conv_in_fwd(x, params + nt.L[L_IN0].w_off, c.y(L_IN0), training ? c.f(w.partials) : nullptr, B, H, W, s,
+                               c.nf() + NF_IMAGE));
   if (training) SIFSR_TRY(bn_unit_finalize(c, L_IN0, conv_in_fwd_blocks(B, H, W), running, momentum, eps));
   SIFSR_TRY(conv_unit_fwd(c, L_IN3, src_act(c, L_IN0), src_none(), training, running, momentum, eps));
 
@@ -635,7 +640,7 @@ int sifsr_engine_forward(const float* x, float* sr, const float* params, float* 
 
   // outlay (model.py:605)
   SIFSR_TRY(launch_conv_out_fwd(c.y(L_U3B), c.scale(L_U3B), c.shift(L_U3B), params + nt.out_w_off,
-                                params + nt.out_b_off, sr, B, H, W, s));
+                                params + nt.out_b_off, sr, B, H, W, s, c.nf()));
   return SIFSR_OK;
 }
 
@@ -704,11 +709,11 @@ int sifsr_engine_backward(const float* x, const float* dsr, const float* params,
     int nblk = B * ((H + 15) / 16) * ((W + 15) / 16);
     if (nblk > 768) nblk = 768;   // persistent: three 168-register workgroups per CU (fused_edges.hip)
     SIFSR_TRY(launch_tail_bwd_reduce(c.y(L_U3B), c.scale(L_U3B), c.shift(L_U3B), c.mean(L_U3B), c.invstd(L_U3B), dsr,
-                                     params + nt.out_w_off, c.f(w.slabs), c.f(w.partials), nblk, B, H, W, s));
+                                     params + nt.out_w_off, c.f(w.slabs), c.f(w.partials), nblk, B, H, W, s, c.nf()));
     if (grads + nt.out_b_off != grads + nt.out_w_off + 144) return SIFSR_ERR_ARG;
     SIFSR_TRY(launch_bn_bwd_finalize(c.f(w.partials), nblk, 16, (double)w.npix[0], c.scale(L_U3B), c.mean(L_U3B), c.invstd(L_U3B),
                                      grads + L.gamma_off, grads + L.beta_off, c.coef(), s, c.shift(L_U3B), params + L.beta_off,
-                                     c.coef_f(L_U3B), c.f(w.slabs), 145, grads + nt.out_w_off, c.frozen));   // (+ outlay dW / db)
+                                     c.coef_f(L_U3B), c.f(w.slabs), 145, grads + nt.out_w_off, c.frozen, c.nf()));   // (+ outlay dW / db)
     if (!tail_in_bwd16)
       SIFSR_TRY(launch_tail_bwd_apply(c.y(L_U3B), c.scale(L_U3B), c.shift(L_U3B), c.coef(), dsr, params + nt.out_w_off, c.g(L_U3B),
                                       B, H, W, s));
@@ -794,7 +799,7 @@ int sifsr_engine_backward(const float* x, const float* dsr, const float* params,
                                      c.f(w.partials), nblk_r, s));
       SIFSR_TRY(launch_bn_bwd_finalize(c.f(w.partials), nblk_r, 16, (double)npix, c.scale(L_IN0), c.mean(L_IN0), c.invstd(L_IN0),
                                        grads + L.gamma_off, grads + L.beta_off, c.coef(), s, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
-                                       c.frozen));
+                                       c.frozen, c.nf()));
     }
     int nblk = B * ((H + 15) / 16) * ((W + 15) / 16);
     if (head_linear) {      // g[L_IN0] holds dz

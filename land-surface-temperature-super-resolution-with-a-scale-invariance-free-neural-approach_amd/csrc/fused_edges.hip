@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256, 3) void tail_bwd_reduce_kernel(const float* __
                                                                  const float* __restrict__ invstd,
                                                                  const float* __restrict__ dsr, const float* __restrict__ w,
                                                                  float* __restrict__ wpart, float* __restrict__ bnpart,
-                                                                 int B, int H, int W) {
+                                                                 int B, int H, int W, int* __restrict__ nf) {
   __shared__ float dt[2][328];
   __shared__ double dred[4][4][48];       // [wave][channel quad][dW 4 x 9 | db | pad | sum dz x4 | sum dz*y x4]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -200,7 +200,10 @@ __global__ __launch_bounds__(256, 3) void tail_bwd_reduce_kernel(const float* __
     const int ci = tid / 9, t = tid % 9;
     wpart[(size_t)blockIdx.x * 145 + tid] = (float)wsum(ci >> 2, (ci & 3) * 9 + t);
   } else if (tid == 144) {
-    wpart[(size_t)blockIdx.x * 145 + 144] = (float)wsum(0, 36);
+    // the bias gradient = the sum of every d loss / d sr this workgroup read: not finite if one of them is not (common.h)
+    const float db = (float)wsum(0, 36);
+    wpart[(size_t)blockIdx.x * 145 + 144] = db;
+    if (nf != nullptr && nonfinite(db)) nf[NF_BATCH] = 1;
   } else if (tid >= 192 && tid < 208) {
     // channel c: sum dz and sum dz*xhat = invstd * (sum dz*y - mean * sum dz), in float64
     const int c = tid - 192, q = c >> 2, j = c & 3;
@@ -258,10 +261,10 @@ __global__ __launch_bounds__(256) void tail_bwd_apply_kernel(const float* __rest
 
 int launch_tail_bwd_reduce(const float* y, const float* scale, const float* shift, const float* mean, const float* invstd,
                            const float* dsr, const float* w, float* wpart, float* bnpart, int nblk, int B, int H, int W,
-                           hipStream_t s) {
+                           hipStream_t s, int* nf) {
   if (H < 3 || W < 3 || nblk < 1) return SIFSR_ERR_SHAPE;
   const bool full = H % 16 == 0 && W % 16 == 0;
-#define TAIL_REDUCE(HS_, FULL_) hipLaunchKernelGGL((tail_bwd_reduce_kernel<HS_, FULL_>), dim3(nblk), dim3(256), 0, s, y, scale, shift, mean, invstd, dsr, w, wpart, bnpart, B, H, W)
+#define TAIL_REDUCE(HS_, FULL_) hipLaunchKernelGGL((tail_bwd_reduce_kernel<HS_, FULL_>), dim3(nblk), dim3(256), 0, s, y, scale, shift, mean, invstd, dsr, w, wpart, bnpart, B, H, W, nf)
   if (sifsr_half_storage()) { if (full) TAIL_REDUCE(true, true); else TAIL_REDUCE(true, false); }
   else { if (full) TAIL_REDUCE(false, true); else TAIL_REDUCE(false, false); }
 #undef TAIL_REDUCE

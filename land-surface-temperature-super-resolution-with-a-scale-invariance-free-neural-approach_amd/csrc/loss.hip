@@ -21,7 +21,8 @@ constexpr int LS = TP + 1;     // LDS row stride
 
 __device__ __forceinline__ int refl(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
 __device__ __forceinline__ float huber_val(float e) { const float a = fabsf(e); return a < 1.f ? 0.5f * e * e : a - 0.5f; }
-__device__ __forceinline__ float clamp1(float e) { return fminf(fmaxf(e, -1.f), 1.f); }
+// (comparisons, not fminf / fmaxf: those return the other operand for a NaN, and a NaN residual must stay one -- nn.HuberLoss's gradient)
+__device__ __forceinline__ float clamp1(float e) { return e < -1.f ? -1.f : (e > 1.f ? 1.f : e); }
 
 struct Taps { float w[9]; };
 __device__ __forceinline__ float k4(int a) { return (a == 0 || a == 3) ? -0.09375f : 0.59375f; }

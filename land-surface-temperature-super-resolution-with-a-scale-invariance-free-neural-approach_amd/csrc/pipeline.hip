@@ -74,6 +74,15 @@ __global__ __launch_bounds__(256) void l4pool4_kernel(const float* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // PSNR / SSIM
 // ---------------------------------------------------------------------------------------------
+// min / max that keep a NaN (fminf / fmaxf drop it): numpy's, which skimage's data range is taken with.  The MASKED instantiation
+// keeps fminf / fmaxf: what a valid NaN pixel does there is the scores family's contract (include/sifsr_scores.h).
+template <bool MASKED> __device__ __forceinline__ float mm_min(float a, float b) {
+  if constexpr (MASKED) return fminf(a, b); else return (a != a || b != b) ? a + b : fminf(a, b);
+}
+template <bool MASKED> __device__ __forceinline__ float mm_max(float a, float b) {
+  if constexpr (MASKED) return fmaxf(a, b); else return (a != a || b != b) ? a + b : fmaxf(a, b);
+}
+
 template <bool MASKED>
 __global__ __launch_bounds__(256) void minmax_partial_kernel(const float* __restrict__ t, size_t n, float* __restrict__ part,
                                                              const unsigned char* __restrict__ valid, int H, int W, int scale) {
@@ -87,24 +96,25 @@ __global__ __launch_bounds__(256) void minmax_partial_kernel(const float* __rest
       if (!valid[((r / H) * (H / scale) + y / scale) * (W / scale) + x / scale]) continue;
     }
     const float v = t[e];
-    lo = fminf(lo, v); hi = fmaxf(hi, v);
+    lo = mm_min<MASKED>(lo, v); hi = mm_max<MASKED>(hi, v);
   }
   smin[threadIdx.x] = lo; smax[threadIdx.x] = hi;
   __syncthreads();
   for (int st = 128; st > 0; st >>= 1) {
     if ((int)threadIdx.x < st) {
-      smin[threadIdx.x] = fminf(smin[threadIdx.x], smin[threadIdx.x + st]);
-      smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + st]);
+      smin[threadIdx.x] = mm_min<MASKED>(smin[threadIdx.x], smin[threadIdx.x + st]);
+      smax[threadIdx.x] = mm_max<MASKED>(smax[threadIdx.x], smax[threadIdx.x + st]);
     }
     __syncthreads();
   }
   if (threadIdx.x == 0) { part[2 * blockIdx.x] = smin[0]; part[2 * blockIdx.x + 1] = smax[0]; }
 }
 
+template <bool MASKED>
 __global__ void minmax_final_kernel(float* __restrict__ part, int n) {
   if (threadIdx.x == 0) {
     float lo = INFINITY, hi = -INFINITY;
-    for (int i = 0; i < n; ++i) { lo = fminf(lo, part[2 * i]); hi = fmaxf(hi, part[2 * i + 1]); }
+    for (int i = 0; i < n; ++i) { lo = mm_min<MASKED>(lo, part[2 * i]); hi = mm_max<MASKED>(hi, part[2 * i + 1]); }
     part[512] = lo; part[513] = hi;
   }
 }
@@ -303,7 +313,7 @@ int launch_psnr_ssim(const float* pred, const float* targ, int B, int H, int W, 
   if (mmb < 1) mmb = 1;
   const dim3 grid((W + MT - 1) / MT, (H + MT - 1) / MT, B);
   hipLaunchKernelGGL(minmax_partial_kernel<false>, dim3(mmb), dim3(256), 0, s, targ, n, mm, (const unsigned char*)nullptr, H, W, 1);
-  hipLaunchKernelGGL(minmax_final_kernel, dim3(1), dim3(64), 0, s, mm, mmb);
+  hipLaunchKernelGGL(minmax_final_kernel<false>, dim3(1), dim3(64), 0, s, mm, mmb);
   hipLaunchKernelGGL(psnr_ssim_tile_kernel<false>, grid, dim3(256), 0, s, pred, targ, mm, H, W, part,
                      (const unsigned char*)nullptr, 1, (int*)nullptr);
   hipLaunchKernelGGL(psnr_ssim_final_kernel<false>, dim3(1), dim3(256), 0, s, part, (int)(grid.x * grid.y), B, H, W, mm, out2,
@@ -332,7 +342,7 @@ int launch_psnr_ssim_masked(const float* pred, const float* targ, const unsigned
   if (mmb > 256) mmb = 256;
   if (mmb < 1) mmb = 1;
   hipLaunchKernelGGL(minmax_partial_kernel<true>, dim3(mmb), dim3(256), 0, s, targ, n, mm, valid, H, W, scale);
-  hipLaunchKernelGGL(minmax_final_kernel, dim3(1), dim3(64), 0, s, mm, mmb);
+  hipLaunchKernelGGL(minmax_final_kernel<true>, dim3(1), dim3(64), 0, s, mm, mmb);
   hipLaunchKernelGGL(psnr_ssim_tile_kernel<true>, grid, dim3(256), 0, s, pred, targ, (const float*)mm, H, W, part, valid, scale, pcnt);
   hipLaunchKernelGGL(psnr_ssim_final_kernel<true>, dim3(1), dim3(256), 0, s, (const double*)part, (int)tiles, B, H, W,
                      (const float*)mm, out2, (const int*)pcnt, counts2);

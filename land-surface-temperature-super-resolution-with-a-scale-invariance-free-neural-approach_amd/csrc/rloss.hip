@@ -51,7 +51,7 @@ struct RlArgs {
 };
 
 __device__ __forceinline__ double huber_d(double e) { const double a = fabs(e); return a < 1.0 ? 0.5 * e * e : a - 0.5; }
-__device__ __forceinline__ double clamp_d(double e) { return fmin(fmax(e, -1.0), 1.0); }
+__device__ __forceinline__ double clamp_d(double e) { return e < -1.0 ? -1.0 : (e > 1.0 ? 1.0 : e); }   // (a NaN residual stays NaN, as in loss.hip)
 __host__ __device__ __forceinline__ long long cdiv_ll(long long a, long long b) { return (a + b - 1) / b; }
 
 // s1 = 1 / n1, s2 = 1 / (F n2) from the counts on the device (or the unmasked ones, by the same expressions); a count <= 0: both 0

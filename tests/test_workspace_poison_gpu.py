@@ -7,7 +7,9 @@ scratch, which runs from the 256-byte-aligned end of U[2] (region 25 of sifsr_mo
 resolution) to workspace_bytes(training = 0).  (engine.hip: every use the backward makes of that scratch starts with a kernel of the
 backward writing it -- the tail reduction, bn_bwd_reduce, the fused 16 -> 16 kernel's and the upsample adjoint's rows; the forward's
 statistics live on in mean / invstd / scale / shift.  The workspace holds floating-point data only -- fp32, bf16, the float64
-coefficients -- no counters, indices or addresses, so a poisoned value cannot steer an access.)
+coefficients -- and, behind `shift`, the 1 + B + 1024 int flag words of non-finite data (include/sifsr_hip.h), which the first launch
+of the forward clears or writes before anything reads them and which are only ever compared with zero; no counters, indices or
+addresses, so a poisoned value cannot steer an access.)
 
 sr, the running statistics, nbt and all 282,705 gradients must be bit-identical under zeros, NaN and N(0,1) poison and NaN-free, no
 guard byte may change, and x, params, dsr must come back untouched.  No tolerance anywhere; none of this needs the oracle."""
