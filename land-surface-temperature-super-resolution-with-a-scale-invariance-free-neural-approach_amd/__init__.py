@@ -46,6 +46,9 @@ Drop-in surface (SURVEY.md §8 b):
   rconserve.consistency / conserve, ratio.predict_granule(conserve=) / ratio.predict_granule_gaps(conserve=)  <- no counterpart:
                                        the residual LST - D(SR) and its correction at any ratio H / h <= 8, with the sensor model of
                                        degrade and the resampler of ratio (include/sifsr_rconserve.h)
+  rproducts.decode / PatchMiner / patch_counts / expand_valid, MinedPatches(hr=), rloss.train_epoch / eval_epoch / fit  <- no
+                                       counterpart: mining at any ratio hr / window with the reference's window and acceptance
+                                       rules, loaders and the epoch loop on the patches (include/sifsr_rproducts.h)
   products.decode / PatchMiner / MinedPatches, dataset.MinedDataset  <- process_modis.py:38-335, data_preparation.py:32-102
                                        (raw granule arrays -> patches + statistics.json, on device)
 
@@ -56,7 +59,7 @@ and registers ``sifsr`` / ``sifsr.<submodule>`` as aliases of the same module ob
 import importlib
 import sys
 
-_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "degrade", "predict", "baselines", "products", "lpips", "adapt", "sensor", "rconserve", "ratio", "rloss")
+_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "degrade", "predict", "baselines", "products", "lpips", "adapt", "sensor", "rconserve", "ratio", "rloss", "rproducts")
 for _m in _SUBMODULES:
     importlib.import_module(__name__ + "." + _m)
 

@@ -38,6 +38,7 @@ FAMILIES = {
     "ratio": ("sifsr_ratio.h", "sifsrr_"),
     "rloss": ("sifsr_rloss.h", "sifsrq_"),
     "rconserve": ("sifsr_rconserve.h", "sifsrc_"),
+    "rproducts": ("sifsr_rproducts.h", "sifsrn_"),
 }
 ABI_VERSION = 3
 # the entry points whose int return is a count, not a status: call() raises on a non-zero int from every other one

@@ -15,6 +15,8 @@ import torch
 import torch.nn.functional as F
 from torch.utils.data import Dataset
 
+from . import _lib
+
 # statistics of the 83 shipped MODIS/ASTER test pairs (SURVEY.md §8 c), used as synthetic constants
 DEFAULT_STATS = {"mean_lst": 307.2378, "std_lst": 5.5698, "mean_ndvi": 0.6452, "std_ndvi": 0.1683}
 
@@ -72,6 +74,9 @@ class MinedDataset(Dataset):
     ``mined.statistics("Train", valid_only=True)``."""
 
     def __init__(self, mined, split="Train", stats=None, masked=False):
+        if getattr(mined, "hr", 4 * mined.window) != 4 * mined.window:
+            raise _lib.SifsrError(f"MinedDataset is the host path at x4 (a CPU bicubic of scale 4): patches of window {mined.window} and "
+                                  f"hr {mined.hr} go through MinedPatches.loader / masked_loader and rloss.train_epoch")
         self.split, self.masked = split, bool(masked)
         self.stats = dict(stats) if stats is not None else mined.statistics("Train", valid_only=self.masked)
         rows = mined.rows(split)

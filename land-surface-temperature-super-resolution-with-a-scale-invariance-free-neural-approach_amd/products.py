@@ -20,6 +20,10 @@ the valid pixels of every patch, fill the others with a neutral local mean (the 
 moments of the valid pixels; `statistics(valid_only=True)` merges those, and `masked_loader` yields the filled input with the mask
 and the count of valid pixels for `train.train_step(..., valid, n_valid)`.
 
+At a ratio other than x4 the miner is `sifsr.rproducts.PatchMiner`; it returns the `MinedPatches` of this module
+with `hr` set, and `statistics`, `fill`, `loader` and `masked_loader` follow `hr`: the NDVI count of a patch, the resampler of
+`lst_up` (`ratio.prepare_tiles`) and, for masked batches, the (2,) counts of `rloss.valid_counts` in place of the one count.
+
 Window order and `k` are the reference generator's (us.split), see the header: on a square raster column blocks are outer, row
 blocks inner, and the ragged edge windows are counted but never accepted.
 """
@@ -31,7 +35,7 @@ import random
 import numpy as np
 import torch
 
-from . import _lib, pipeline
+from . import _lib, pipeline, ratio
 
 QC_MODES = {"MOD21A1D": 0, "MOD11A1": 1}
 STAT_KEYS = ("maxi", "mini", "mean_lst", "std_lst", "mean_ndvi", "std_ndvi")
@@ -84,6 +88,14 @@ def decode(lst_raw, nir, red, clip=False):
     ndvi = torch.empty((4 * h, 4 * w), dtype=torch.float32, device=lst_raw.device)
     _lib.call("sifsrp_decode", lst_raw, nir, red, lst_k, ndvi, h, w, 1 if clip else 0, _lib.stream_ptr(lst_raw.device))
     return lst_k, ndvi
+
+
+def _patch_counts(valid, window, hr):
+    """valid (N,1,w,w) or (N,w,w) uint8 on the device -> (N,2) int64 on the device, row n = {n1, n2} of patch n under an hr x hr
+    patch (`sifsrn_patch_counts`; nothing is read back)"""
+    counts = torch.empty((valid.shape[0], 2), dtype=torch.int64, device=valid.device)
+    _lib.call("sifsrn_patch_counts", valid.contiguous(), counts, valid.shape[0], int(window), int(hr), _lib.stream_ptr(valid.device))
+    return counts
 
 
 def fill_patches(lst):
@@ -181,25 +193,36 @@ def merge_moments(count, mean, m2):
 
 
 class MinedPatches:
-    """lst (N,1,w,w) Kelvin and ndvi (N,1,4w,4w) in [-1,1], float32 device tensors; index (N,4) int64 [granule id, k, row0, col0];
+    """lst (N,1,w,w) Kelvin and ndvi (N,1,hr,hr) in [-1,1], float32 device tensors; index (N,4) int64 [granule id, k, row0, col0];
     moments (N,8) float64 (the rows of sifsrp_gather); split: None until `assign_split`, then an (N,) array of 'Train' / 'Val'.
+    `hr`: the side of the NDVI patch, None = 4 w (what `PatchMiner` mines; `rproducts.PatchMiner` sets another).
     After `fill()`: filled (N,1,w,w) float32 and valid (N,1,w,w) uint8 device tensors, valid_moments (N,5) float64 on the host
     ([count, mean, M2, min, max] over the valid pixels of each patch)."""
 
-    def __init__(self, lst, ndvi, index, moments, window=64):
+    def __init__(self, lst, ndvi, index, moments, window=64, hr=None):
         self.lst, self.ndvi, self.index, self.moments, self.window = lst, ndvi, index, moments, int(window)
+        self.hr = 4 * self.window if hr is None else int(hr)
+        if self.hr < self.window:
+            raise _lib.SifsrError(f"MinedPatches: hr {hr} is smaller than the window {window}")
         self.split = None
-        self.filled = self.valid = self.valid_moments = self._valid_counts = None
+        self.filled = self.valid = self.valid_moments = self._valid_counts = self._patch_counts = None
 
     def fill(self):
         """`fill_patches` over all patches, once: sets and caches `.filled`, `.valid`, `.valid_moments` (one read-back of 40 bytes
-        per patch; the counts also stay on the device for the masked loader).  Returns self."""
+        per patch; the counts also stay on the device for the masked loader).  The fill is LR-only, whatever `hr`.  Returns self."""
         if self.filled is None:
             filled, valid, moments = fill_patches(self.lst)
             self._valid_counts = moments[:, 0].to(torch.int64)
             self.valid_moments = moments.cpu().numpy()
             self.filled, self.valid = filled, valid
         return self
+
+    def patch_counts(self):
+        """(N,2) int64 on the device, row n = {n1, n2} of patch n: its valid cells and the HR pixels of its hr x hr patch under
+        them -- `rloss.valid_counts` of that patch alone (`sifsrn_patch_counts`), formed once after `fill()` and kept."""
+        if self._patch_counts is None:
+            self._patch_counts = _patch_counts(self.fill().valid, self.window, self.hr)
+        return self._patch_counts
 
     def __len__(self):
         return int(self.index.shape[0])
@@ -236,7 +259,11 @@ class MinedPatches:
             if n == 0:
                 raise _lib.SifsrError(f"statistics: no valid LST pixel in split {split!r}")
             maxi, mini = float(v[:, 4].max()), float(v[:, 3].min())
-        nn, mean_n, m2_n = merge_moments(16.0 * m[:, 0], m[:, 5], m[:, 6])
+        if self.hr == 4 * self.window:
+            n_ndvi = 16.0 * m[:, 0]
+        else:                                                            # (hr / window)^2 count: hr^2 for a patch, in integers
+            n_ndvi = (m[:, 0] * float(self.hr * self.hr)) / float(self.window * self.window)
+        nn, mean_n, m2_n = merge_moments(n_ndvi, m[:, 5], m[:, 6])
         return {"maxi": maxi, "mini": mini, "mean_lst": float(mean_l),
                 "std_lst": float(math.sqrt(m2_l / n)), "mean_ndvi": float(mean_n), "std_ndvi": float(math.sqrt(m2_n / nn))}
 
@@ -255,15 +282,23 @@ class PatchLoader:
 
     `masked`: batches of five, (lst_norm, lst_up, ndvi_norm, valid (b,1,w,w) uint8, n_valid): lst_norm is the z-scored FILLED patch
     (`MinedPatches.fill`), lst_up its bicubic x4, and n_valid a 0-d int64 device tensor, the number of valid LST pixels of the batch
-    -- the sum of the selected rows' counts, formed on the device without a host read."""
+    -- the sum of the selected rows' counts, formed on the device without a host read.
+
+    `mined.hr != 4 * mined.window` (patches of `rproducts.PatchMiner`): lst_up is (b,1,hr,hr), the bicubic resampling of
+    `ratio.prepare_tiles` / `ratio.upsample` -- the operator `ratio.predict_granule` feeds the network with --, and the fifth item
+    of a masked batch is the int64 (2,) sum of the selected rows of `MinedPatches.patch_counts()`, equal to
+    `rloss.valid_counts(valid, (hr, hr))` of the batch: what `rloss.train_step(..., valid=, counts=)` takes."""
 
     def __init__(self, mined, split, batch, stats, shuffle=True, seed=0, masked=False):
         self.mined, self.rows, self.batch, self.stats = mined, mined.rows(split), int(batch), dict(stats)
         self.shuffle, self.seed, self.epoch, self.masked = bool(shuffle), int(seed), 0, bool(masked)
         if self.batch < 1:
             raise ValueError(f"batch must be positive, got {batch}")
+        self.x4 = mined.hr == 4 * mined.window
         if self.masked:
             mined.fill()
+            if not self.x4:
+                mined.patch_counts()
 
     def __len__(self):
         return -(-len(self.rows) // self.batch)
@@ -280,8 +315,9 @@ class PatchLoader:
             src = m.filled if self.masked else m.lst
             lst = (src.index_select(0, sel) - float(st["mean_lst"])) / float(st["std_lst"])
             ndvi = (m.ndvi.index_select(0, sel) - float(st["mean_ndvi"])) / float(st["std_ndvi"])
-            x = pipeline.prepare_tiles(lst, ndvi)                       # unit statistics: channel 0 = bicubic x4 of lst
+            x = (pipeline if self.x4 else ratio).prepare_tiles(lst, ndvi)   # unit statistics: channel 0 = bicubic of lst to (hr, hr)
             if self.masked:
-                yield lst, x[:, 0:1].contiguous(), ndvi, m.valid.index_select(0, sel), m._valid_counts.index_select(0, sel).sum()
+                n_valid = m._valid_counts.index_select(0, sel).sum() if self.x4 else m.patch_counts().index_select(0, sel).sum(0)
+                yield lst, x[:, 0:1].contiguous(), ndvi, m.valid.index_select(0, sel), n_valid
             else:
                 yield lst, x[:, 0:1].contiguous(), ndvi

@@ -18,8 +18,9 @@ device; CPU tensors raise SifsrError: there is no CPU path.
 
 Fine-tuning on a granule at a ratio and masks in the loss at a ratio are ``sifsr.rloss``; the consistency check
 and the residual correction at a ratio are ``sifsr.rconserve`` (§9 f20), which the two granule calls take as the keyword-only
-option ``conserve=k``.  Out of scope here:
-a captured ``GranulePredictor`` at a ratio, ``GraphedTrainStep`` at a ratio, mining patches at a ratio,
+option ``conserve=k``; mining training patches at a ratio, their loaders and the epoch loop are ``sifsr.rproducts`` and
+``rloss.train_epoch`` / ``fit`` (§9 f22).  Out of scope here:
+a captured ``GranulePredictor`` at a ratio, ``GraphedTrainStep`` at a ratio,
 ratios that are not ``hr / window`` for such a pair (926.25 / 90 and 231.656 / 90 stay with ``sifsr.degrade``), rerouting the
 drop-ins, and bf16."""
 from __future__ import annotations

@@ -5,6 +5,9 @@ a partly valid patch -- in one call with its gradient.
     valid_counts(valid, hr_shape)      (n1, n2) on the device: the valid LR cells and the HR pixels under them
     sif_loss_with_grad / sif_loss      the loss block at ``factor``, optionally over the valid cells only
     train_step                         ``sensor.train_step`` with the fused loss, ``valid=`` for cloudy patches (``train._optimise``)
+    eval_step / train_epoch / eval_epoch / fit
+                                       ``train.eval_step`` / ``train_epoch`` / ``eval_epoch`` / ``fit`` at ``factor``, over the loaders
+                                       of patches mined at a ratio (``sifsr.rproducts``)
     adapt_granule                      ``adapt.adapt_granule`` at ratio hr / window: its own checks, then the same loop
 
 The LR cell of HR pixel (Y, X) is (Y h // H, X w // W): the rule under which ``ratio.predict_granule_gaps`` masks its output.
@@ -14,12 +17,12 @@ fp32 on the device; CPU tensors raise SifsrError: there is no CPU path.
 
 The consistency check and the residual correction at a ratio are ``sifsr.rconserve``.
 Out of scope here: ``GraphedTrainStep`` at a ratio (the call itself can be captured), a captured
-``GranulePredictor`` at a ratio, mining patches at a ratio, the ``hkw`` argument in the loss, and bf16."""
+``GranulePredictor`` at a ratio, the ``hkw`` argument in the loss, and bf16."""
 from __future__ import annotations
 
 import torch
 
-from . import _lib, adapt, gaps, ratio, sensor, train
+from . import _lib, adapt, gaps, metrics, ratio, rproducts, sensor, train
 
 MAX_FACTOR = 8.0
 MAX_SIDE = 16384
@@ -176,6 +179,93 @@ def train_step(model, optimizer, lst, lst_up, ndvi, stats, alpha, gamma, factor,
         return losses[0], losses[1], losses[2], dsr
 
     return train._optimise(model, optimizer, lst_up, ndvi, loss_fn, sync_grads, return_sr)
+
+
+@torch.inference_mode()
+def eval_step(model, lst, lst_up, ndvi, stats, alpha, gamma, factor, kind="sr2", valid=None, counts=None):
+    """``train.eval_step`` at ``factor``: eval mode, no gradient, -> (ds, pl, loss) as device scalars.  ``valid`` / ``counts``: as
+    ``train_step`` (``counts=None`` with ``valid``: formed by ``valid_counts``)."""
+    model.eval()
+    sr = model(torch.cat((lst_up, ndvi), dim=1))
+    return _eval_losses(sr, lst, ndvi, stats, alpha, gamma, factor, kind, valid, counts, "eval_step")
+
+
+def _eval_losses(sr, lst, ndvi, stats, alpha, gamma, factor, kind, valid, counts, what):
+    sr, lst, ndvi = sr.contiguous(), lst.contiguous(), ndvi.contiguous()
+    k, B, H, W, f, v, c = _args(kind, sr, lst, ndvi, factor, valid, counts, what)
+    losses, _ = _call(k, sr, lst, ndvi, B, H, W, f, stats["mean_lst"], stats["std_lst"], alpha, gamma, v, c, False)
+    return losses[0], losses[1], losses[2]
+
+
+def _unpack_batch(batch, device):
+    """``train._unpack_batch`` for the batches of a loader at a ratio: the fifth item is the (2,) counts of ``valid_counts``, or
+    (b,2) per-patch rows that are summed on the device; nothing is read back."""
+    if len(batch) not in (3, 5):
+        raise _lib.SifsrError(f"a batch has 3 or 5 items, got {len(batch)}")
+    lst, lst_up, ndvi = (t.to(device) for t in batch[:3])
+    if len(batch) == 3:
+        return lst, lst_up, ndvi, None, None
+    valid, counts = batch[3].to(device), batch[4].to(device=device, dtype=torch.int64)
+    if counts.shape[-1:] != (2,) or counts.dim() not in (1, 2):
+        raise _lib.SifsrError(f"the fifth item of a batch at a ratio is the (2,) counts of valid_counts or (b,2) rows, got {tuple(counts.shape)}")
+    return lst, lst_up, ndvi, valid, (counts.sum(0) if counts.dim() == 2 else counts).contiguous()
+
+
+def _score(sr, lst_up, valid, masked_metrics, acc, den):
+    """``train._score`` with the LR mask expanded to the HR mask ``metrics.masked_psnr_ssim`` takes at scale 1"""
+    if masked_metrics and valid is not None:
+        valid = rproducts.expand_valid(valid, sr.shape[-2:])
+    train._score(sr, lst_up, valid, masked_metrics, acc, den)
+
+
+def train_epoch(model, loader, optimizer, stats, alpha, gamma, factor, kind="sr2", device="cuda", with_metrics=True,
+                masked_metrics=False):
+    """``train.train_epoch`` at ``factor``: one ``rloss.train_step`` per batch of ``loader`` (``MinedPatches.loader`` /
+    ``masked_loader`` of patches mined by ``rproducts.PatchMiner``; batches of three, or of five with the counts), -> the epoch means
+    (ds_loss, percep_loss, loss, psnr, ssim), read back ONCE per epoch.  PSNR / SSIM score the training-mode prediction against
+    ``lst_up``; ``masked_metrics``: over the HR pixels under valid cells only (``rproducts.expand_valid``, then
+    ``metrics.masked_psnr_ssim``)."""
+    acc = torch.zeros(5, dtype=torch.float64, device=device)
+    den = torch.zeros(5, dtype=torch.float64, device=device)
+    n = 0
+    for batch in loader:
+        lst, lst_up, ndvi, valid, counts = _unpack_batch(batch, device)
+        ds, pl, loss, sr = train_step(model, optimizer, lst, lst_up, ndvi, stats, alpha, gamma, factor, kind, valid=valid, counts=counts,
+                                      return_sr=True)
+        acc[0] += ds.detach(); acc[1] += pl.detach(); acc[2] += loss.detach()
+        if with_metrics:
+            _score(sr, lst_up, valid, masked_metrics, acc, den)
+        n += 1
+    return train._epoch_means(acc, den, n, with_metrics)
+
+
+@torch.inference_mode()
+def eval_epoch(model, loader, stats, alpha, gamma, factor, kind="sr2", device="cuda", with_metrics=True, masked_metrics=False):
+    """``train.eval_epoch`` at ``factor``: eval mode, no gradient; the epoch means of (ds_loss, percep_loss, loss, psnr, ssim)."""
+    model.eval()
+    acc = torch.zeros(5, dtype=torch.float64, device=device)
+    den = torch.zeros(5, dtype=torch.float64, device=device)
+    n = 0
+    for batch in loader:
+        lst, lst_up, ndvi, valid, counts = _unpack_batch(batch, device)
+        sr = model(torch.cat((lst_up, ndvi), dim=1))
+        ds, pl, loss = _eval_losses(sr, lst, ndvi, stats, alpha, gamma, factor, kind, valid, counts, "eval_epoch")
+        acc[0] += ds; acc[1] += pl; acc[2] += loss
+        if with_metrics:
+            _score(sr, lst_up, valid, masked_metrics, acc, den)
+        n += 1
+    return train._epoch_means(acc, den, n, with_metrics)
+
+
+def fit(model, train_loader, val_loader, n_epochs, optimizer, stats, alpha, gamma, factor, kind="sr2", checkpoint=None,
+        masked_metrics=False):
+    """``train.fit`` at ``factor`` over two loaders (``MinedPatches.loader`` / ``masked_loader``, which shuffle per epoch themselves):
+    per epoch one ``train_epoch`` and one ``eval_epoch``, the same ``metrics`` dict, ``best_epoch`` rule and restore of the best
+    state through ``checkpoint`` (``train.ModelCheckpoint``).  Returns (model, metrics)."""
+    device = next(model.parameters()).device
+    return train._fit(model, n_epochs, checkpoint,
+                      lambda: train_epoch(model, train_loader, optimizer, stats, alpha, gamma, factor, kind, device, masked_metrics=masked_metrics),
+                      lambda: eval_epoch(model, val_loader, stats, alpha, gamma, factor, kind, device, masked_metrics=masked_metrics))
 
 
 def adapt_granule(model, lst_g, ndvi_g, stats, window, hr, mask=None, steps=20, lr=1e-5, alpha=0.5, gamma=1.0, kind="sr2", batch=16,

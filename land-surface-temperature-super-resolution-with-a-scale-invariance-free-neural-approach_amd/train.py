@@ -200,12 +200,20 @@ def fit(model, train_dataset, val_dataset, n_epochs, batch_size, optimizer, alph
     tl = DataLoader(train_dataset, batch_size=batch_size, shuffle=shuffle, generator=generator)
     vl = DataLoader(val_dataset, batch_size=batch_size, shuffle=shuffle, generator=generator)
     stats = train_dataset.stats
+    return _fit(model, n_epochs, checkpoint,
+                lambda: train_epoch(model, tl, optimizer, stats, alpha, gamma, kind, device, masked_metrics=masked_metrics),
+                lambda: eval_epoch(model, vl, stats, alpha, gamma, kind, device, masked_metrics=masked_metrics))
+
+
+def _fit(model, n_epochs, checkpoint, train_pass, val_pass):
+    """The epoch loop under ``fit`` and ``rloss.fit``: ``train_pass()`` / ``val_pass()`` -> the five epoch means; the metrics dict,
+    the ``best_epoch`` rule and the restore of the best state are the reference's (train_model_B_gradFTM.py:338-352)."""
     keys = ("dsloss", "perceploss", "loss", "psnr", "ssim")
     metrics = {f"{split}_{k}": [] for split in ("train", "val") for k in keys}
     for epoch in range(1, n_epochs + 1):
-        for k, v in zip(keys, train_epoch(model, tl, optimizer, stats, alpha, gamma, kind, device, masked_metrics=masked_metrics)):
+        for k, v in zip(keys, train_pass()):
             metrics[f"train_{k}"].append(v)
-        for k, v in zip(keys, eval_epoch(model, vl, stats, alpha, gamma, kind, device, masked_metrics=masked_metrics)):
+        for k, v in zip(keys, val_pass()):
             metrics[f"val_{k}"].append(v)
         if checkpoint is not None:
             checkpoint.test_update(model, metrics, "val_loss", epoch)
