@@ -49,6 +49,11 @@ Drop-in surface (SURVEY.md §8 b):
   rproducts.decode / PatchMiner / patch_counts / expand_valid, MinedPatches(hr=), rloss.train_epoch / eval_epoch / fit  <- no
                                        counterpart: mining at any ratio hr / window with the reference's window and acceptance
                                        rules, loaders and the epoch loop on the patches (include/sifsr_rproducts.h)
+  rloss.GraphedTrainStep, rloss.train_epoch / fit / adapt_granule(graphed=), adapt.adapt_granule(graphed=), ratio.GranulePredictor,
+  predict.GranulePredictor(gaps=)      <- no counterpart: the training step at any ratio and both granule
+                                       predictors as one hipGraph each; the gap-aware predictor forwards a fixed number of slots and
+                                       keeps the active count on the device, so a stream of granules has no host synchronisation
+                                       (host code only: no kernel, no header)
   products.decode / PatchMiner / MinedPatches, dataset.MinedDataset  <- process_modis.py:38-335, data_preparation.py:32-102
                                        (raw granule arrays -> patches + statistics.json, on device)
 

@@ -105,12 +105,17 @@ class Adaptation:
 
 
 def adapt_granule(model, lst_g, ndvi_g, stats, mask=None, steps=20, lr=1e-5, alpha=0.5, gamma=1.0, kind="sr2", batch=16,
-                  window=64, overlap=0, cover_edges=False, optimizer=None):
+                  window=64, overlap=0, cover_edges=False, optimizer=None, graphed=False):
     """``steps`` optimisation steps of the masked SIF loss on the active tiles of one gappy granule (raw LST (h,w) [K], raw NDVI
     (4h,4w), ``mask`` as in ``gaps.fill_gaps``), BatchNorm statistics frozen.  Step i is ``train.train_step(..., valid=, n_valid=)``
     on the min(batch, n_active) tiles from position i * batch of the active list, cyclic, with ``tile_targets``' outputs; the
     optimizer is ``FlatAdam(lr=lr)`` unless one is given.  The read of the active count is the only host synchronisation; no active
-    tile: no step, no forward.  Returns an ``Adaptation``; the model's mode and ``bn_frozen`` are as they were."""
+    tile: no step, no forward.  Returns an ``Adaptation``; the model's mode and ``bn_frozen`` are as they were.
+
+    ``graphed`` (default False: the loop above, bit for bit): after the read of the active count the step is a
+    ``train.GraphedTrainStep(masked=True)`` for min(batch, n_active) tiles -- three eager steps, the fourth captures, the rest
+    replay --; the optimizer is then ``FlatAdam(lr=lr, capturable=True)`` unless one is given, which must be capturable
+    (ValueError before any launch)."""
     _lib.require_gpu(lst_g, "lst granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
     if lst_g.dim() != 2:
         raise _lib.SifsrError(f"lst granule: expected a 2-D raster, got {tuple(lst_g.shape)}")
@@ -121,12 +126,20 @@ def adapt_granule(model, lst_g, ndvi_g, stats, mask=None, steps=20, lr=1e-5, alp
     def step(model, optimizer, lst, xb, vt, n_valid):
         return train.train_step(model, optimizer, lst, xb[:, 0:1], xb[:, 1:2], stats, alpha, gamma, kind, valid=vt, n_valid=n_valid)
 
-    return _adapt(model, lay, step, lst_g, ndvi_g, stats, mask, int(steps), int(batch), lr, optimizer)
+    def captured(model, optimizer, b):
+        g = train.GraphedTrainStep(model, optimizer, b, stats, alpha, gamma, kind, hr=lay.hr, masked=True)
+        return lambda model, optimizer, lst, xb, vt, n_valid: g(lst, xb[:, 0:1], xb[:, 1:2], vt, n_valid)
+
+    return _adapt(model, lay, step, lst_g, ndvi_g, stats, mask, int(steps), int(batch), lr, optimizer, captured if graphed else None)
 
 
-def _adapt(model, lay, step, lst_g, ndvi_g, stats, mask, steps, batch, lr, optimizer):
+def _adapt(model, lay, step, lst_g, ndvi_g, stats, mask, steps, batch, lr, optimizer, captured=None):
     """The loop of ``adapt_granule`` here and in ``rloss`` on the ``_granule.Layout`` ``lay``: fill -> select -> one read of the active
-    count -> the inputs of the active tiles once -> ``steps`` x ``step(model, optimizer, lst, xb, vt, n_valid)`` -> (ds, pl, loss)."""
+    count -> the inputs of the active tiles once -> ``steps`` x ``step(model, optimizer, lst, xb, vt, n_valid)`` -> (ds, pl, loss).
+    ``captured(model, optimizer, b)``: builds the step of the graphed loop, a ``GraphedTrainStep`` for b tiles behind the same call;
+    ``tile_targets`` and the gather of ``xb`` stay outside its graph (their ``first`` changes per step) and feed its static buffers."""
+    if captured is not None and optimizer is not None and not getattr(optimizer, "capturable", False):
+        raise ValueError("adapt_granule(graphed=True) needs FlatAdam(..., capturable=True), or no optimizer")
     filled, valid = gaps.fill_gaps(lst_g, mask)
     _, active, n_active = gaps.select_tiles(valid, lay.window, lay.overlap, lay.cover_edges)
     n = int(n_active.item())                                            # the one host sync
@@ -136,9 +149,11 @@ def _adapt(model, lay, step, lst_g, ndvi_g, stats, mask, steps, batch, lr, optim
     start = model.flat_parameters().detach().clone()
     x = lay.prepare_active(filled, ndvi_g, stats, active, n_active, n)
     if optimizer is None:
-        optimizer = FlatAdam(model.parameters(), lr=lr)
+        optimizer = FlatAdam(model.parameters(), lr=lr, capturable=captured is not None)
     b = min(batch, n)
     with frozen_bn(model):
+        if captured is not None:
+            step = captured(model, optimizer, b)
         for i in range(steps):
             first = (i * batch) % n
             idx = (torch.arange(first, first + b, device=x.device) % n) if first + b > n else slice(first, first + b)

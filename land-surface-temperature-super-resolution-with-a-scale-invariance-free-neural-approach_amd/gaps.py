@@ -71,15 +71,16 @@ def select_tiles(valid, window=64, overlap=0, cover_edges=False):
     return slot, active, n_active
 
 
-def prepare_active_tiles(filled, ndvi_g, stats, active, n_active, cap, window=64, overlap=0, cover_edges=False, clip_ndvi=True):
+def prepare_active_tiles(filled, ndvi_g, stats, active, n_active, cap, window=64, overlap=0, cover_edges=False, clip_ndvi=True, out=None):
     """-> x (cap,2,4win,4win): x[i] = the network input of tile active[i] for i < min(n_active, cap), the rest untouched
-    (``sifsrg_tiles_prepare``); bit-identical to that tile of ``pipeline.granule_to_tiles(filled, ...)``."""
+    (``sifsrg_tiles_prepare``); bit-identical to that tile of ``pipeline.granule_to_tiles(filled, ...)``.  ``out``: a buffer of at
+    least ``cap`` tiles to write into (a captured run's static one); its first ``cap`` tiles are returned."""
     _lib.require_gpu(filled, "filled granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
     pipeline._mosaic_tiles(filled.shape, ndvi_g.shape, window, overlap, cover_edges)
     if int(cap) < 1:
         raise _lib.SifsrError(f"cap must be positive, got {cap}")
     h, w = filled.shape
-    x = torch.empty((int(cap), 2, 4 * window, 4 * window), dtype=torch.float32, device=filled.device)
+    x = pipeline._tile_buffer(out, int(cap), 2, 4 * window, filled.device, "tile buffer")
     _lib.call("sifsrg_tiles_prepare", filled, ndvi_g, x, active, n_active, int(cap), h, w, window, overlap, 1 if cover_edges else 0,
               *pipeline._stats4(stats), 1 if clip_ndvi else 0, _lib.stream_ptr(filled.device))
     return x
@@ -109,7 +110,8 @@ def _tile_layout(lst_shape, ndvi_shape, window, overlap, cover_edges, plain=Fals
     return _granule.Layout(
         window, 4 * window, overlap, cover_edges, tiles, (4 * h, 4 * w),
         lambda lst_g, ndvi_g, stats, out=None: pipeline.granule_to_tiles(lst_g, ndvi_g, stats, window, True, *lay, out)[0],
-        lambda filled, ndvi_g, stats, active, n_active, cap: prepare_active_tiles(filled, ndvi_g, stats, active, n_active, cap, window, *lay),
+        lambda filled, ndvi_g, stats, active, n_active, cap, out=None: prepare_active_tiles(filled, ndvi_g, stats, active, n_active, cap, window,
+                                                                                          *lay, out=out),
         lambda sr, stats, out=None: pipeline.blend_tiles(sr, (h, w), window, stats, *lay, out),
         lambda sr, slot, valid, stats, fill_value: blend_active_tiles(sr, slot, valid, window, stats, *lay, fill_value))
 

@@ -101,56 +101,38 @@ class GraphedPredictor:
         return self.out[:n].clone()
 
 
-class GranulePredictor:
+def _captured_granule(self, model, lst_shape, stats, window, overlap, cover_edges, batch, device, conserve, gaps=False,
+                      fill_value=float("nan")):
+    """``GranulePredictor.__init__``: the checks (before any launch), then ``_granule.CapturedGranule._capture``"""
+    h, w = (int(v) for v in lst_shape)
+    self.lst_shape, self.window = (h, w), int(window)
+    self.overlap, self.cover_edges = int(overlap), bool(cover_edges)
+    if int(conserve) < 0:
+        raise _lib.SifsrError(f"conserve must be a step count >= 0, got {conserve}")
+    lay = _tile_layout((h, w), (4 * h, 4 * w), self.window, self.overlap, self.cover_edges, plain=not gaps)
+    if int(batch) < 1:
+        raise _lib.SifsrError(f"batch must be positive, got {batch}")
+    self._capture(model, lay, (h, w), stats, batch, conserve, None, gaps, fill_value, device or next(model.parameters()).device)
+
+
+class GranulePredictor(_granule.CapturedGranule):
     """``predict_granule`` for ONE granule shape captured into a HIP graph: prepare -> batched eval forwards -> blend, on one
     stream, replayed per granule.  All buffers are static; the tiles are padded with zero tiles to a whole number of batches
     (every forward has the captured batch shape; the padding's predictions are not read).  ``__call__(lst_g, ndvi_g)`` copies
     the rasters in, replays and returns a clone of the output raster -- bit-identical to the eager ``predict_granule`` with the
-    same arguments; ``conserve`` steps are part of the captured chain.  There is no captured form of ``predict_granule_gaps``: a
-    graph cannot have a data-dependent batch count."""
+    same arguments; ``conserve`` steps are part of the captured chain.
 
+    Keyword-only ``gaps=True`` (and ``fill_value``; ``_granule.keyword_options``): the captured form of
+    ``predict_granule_gaps`` with the same arguments -- a graph can have a fixed slot count and a device-side active count: every
+    slot is forwarded, only the active ones are read (``_granule.predict_gaps_fixed``), and no call reads the count back.
+    ``__call__(lst_g, ndvi_g, mask=None, return_info=False)`` then returns the bits of the eager call, ``fill_value`` pixels
+    included; ``info["n_active"]`` is a (1,) int32 device tensor.  The defaults keep the object and the bits above."""
+
+    # the constructor's body is ``_captured_granule`` above: ``__init__`` only states the pinned positional signature, and the
+    # decorator adds ``gaps=`` / ``fill_value=`` around it (fold them into the signature once the pin in the host test may move)
+    @_granule.keyword_options(_captured_granule, gaps=False, fill_value=float("nan"))
     def __init__(self, model, lst_shape, stats, window=64, overlap=0, cover_edges=False, batch=256, device=None, conserve=0):
-        self.model = model.eval()
-        dev = device or next(model.parameters()).device
-        h, w = (int(v) for v in lst_shape)
-        self.lst_shape, self.stats, self.window = (h, w), stats, int(window)
-        self.overlap, self.cover_edges, self.batch = int(overlap), bool(cover_edges), int(batch)
-        self.conserve = int(conserve)
-        if self.conserve < 0:
-            raise _lib.SifsrError(f"conserve must be a step count >= 0, got {conserve}")
-        self.layout = _tile_layout((h, w), (4 * h, 4 * w), self.window, self.overlap, self.cover_edges, plain=True)
-        if self.batch < 1:
-            raise _lib.SifsrError(f"batch must be positive, got {batch}")
-        self.tiles = self.layout.tiles
-        n, hr = self.tiles[0] * self.tiles[1], self.layout.hr
-        self.batch = min(self.batch, n)
-        padded = -(-n // self.batch) * self.batch
-        self.lst = torch.zeros((h, w), dtype=torch.float32, device=dev)
-        self.ndvi = torch.zeros((4 * h, 4 * w), dtype=torch.float32, device=dev)
-        self.x = torch.zeros((padded, 2, hr, hr), dtype=torch.float32, device=dev)
-        self.sr = torch.zeros((padded, 1, hr, hr), dtype=torch.float32, device=dev)
-        self.out = torch.zeros((4 * h, 4 * w), dtype=torch.float32, device=dev)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side), torch.inference_mode():
-            for _ in range(2):                      # warm-up: flat-buffer setup, allocator pools
-                self._run()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.inference_mode(), torch.cuda.graph(self.graph):
-            self._run()
+        """the positional signature (tests/test_conserve_host.py pins its end); ``_captured_granule`` is the body"""
 
-    def _run(self):
-        _granule.predict(self.model, self.layout, self.lst, self.ndvi, self.stats, self.batch, x=self.x, sr=self.sr, out=self.out,
-                         conserve=self.conserve)
-
-    @torch.inference_mode()
-    def __call__(self, lst_g, ndvi_g):
-        h, w = self.lst_shape
-        if tuple(lst_g.shape) != (h, w) or tuple(ndvi_g.shape) != (4 * h, 4 * w):
-            raise ValueError(f"captured for an LST raster {(h, w)} and an NDVI raster {(4 * h, 4 * w)}; got "
-                             f"{tuple(lst_g.shape)}, {tuple(ndvi_g.shape)}")
-        self.lst.copy_(lst_g)
-        self.ndvi.copy_(ndvi_g)
-        self.graph.replay()
-        return self.out.clone()
+    def __call__(self, lst_g, ndvi_g, mask=None, return_info=False):
+        return self._replay(lst_g, ndvi_g, mask, return_info)

@@ -19,8 +19,8 @@ device; CPU tensors raise SifsrError: there is no CPU path.
 Fine-tuning on a granule at a ratio and masks in the loss at a ratio are ``sifsr.rloss``; the consistency check
 and the residual correction at a ratio are ``sifsr.rconserve`` (§9 f20), which the two granule calls take as the keyword-only
 option ``conserve=k``; mining training patches at a ratio, their loaders and the epoch loop are ``sifsr.rproducts`` and
-``rloss.train_epoch`` / ``fit`` (§9 f22).  Out of scope here:
-a captured ``GranulePredictor`` at a ratio, ``GraphedTrainStep`` at a ratio,
+``rloss.train_epoch`` / ``fit`` (§9 f22); ``GranulePredictor`` here is the two granule calls captured into a hipGraph, the
+gap-aware one with no host synchronisation, and ``rloss.GraphedTrainStep`` the captured training step (§9 f23).  Out of scope here:
 ratios that are not ``hr / window`` for such a pair (926.25 / 90 and 231.656 / 90 stay with ``sifsr.degrade``), rerouting the
 drop-ins, and bf16."""
 from __future__ import annotations
@@ -30,7 +30,7 @@ from collections import namedtuple
 
 import torch
 
-from . import _granule, _lib, gaps
+from . import _granule, _lib, gaps, rconserve
 from .rconserve import granule_option
 from .pipeline import _UNIT, _stats4, _tile_buffer
 
@@ -71,11 +71,17 @@ def _layout(lst_g, ndvi_shape, window, hr, overlap, cover_edges):
 
 def _tile_layout(lst_g, ndvi_shape, window, hr, overlap, cover_edges):
     """-> the ``_granule.Layout`` at ratio hr / window of the raster ``lst_g``, or ``_layout``'s SifsrError"""
-    g, shape, lay = _layout(lst_g, ndvi_shape, window, hr, overlap, cover_edges), lst_g.shape, (overlap, cover_edges)
+    return _layout_record(_layout(lst_g, ndvi_shape, window, hr, overlap, cover_edges), lst_g.shape, window, hr, overlap, cover_edges)
+
+
+def _layout_record(g, shape, window, hr, overlap, cover_edges):
+    """the ``_granule.Layout`` of an LST raster of ``shape`` whose ``geometry`` is ``g``"""
+    lay = (overlap, cover_edges)
     return _granule.Layout(
         window, hr, overlap, cover_edges, g.tiles, g.hr_shape,
         lambda lst_g, ndvi_g, stats, out=None: granule_to_tiles(lst_g, ndvi_g, stats, window, hr, True, *lay, out)[0],
-        lambda filled, ndvi_g, stats, active, n_active, cap: prepare_active_tiles(filled, ndvi_g, stats, active, n_active, cap, window, hr, *lay),
+        lambda filled, ndvi_g, stats, active, n_active, cap, out=None: prepare_active_tiles(filled, ndvi_g, stats, active, n_active, cap, window,
+                                                                                          hr, *lay, out=out),
         lambda sr, stats, out=None: blend_tiles(sr, shape, window, hr, stats, *lay, out),
         lambda sr, slot, valid, stats, fill_value: blend_active_tiles(sr, slot, valid, window, hr, stats, *lay, fill_value))
 
@@ -145,15 +151,16 @@ def granule_to_tiles(lst_g, ndvi_g, stats, window, hr, clip_ndvi=True, overlap=0
     return x, (ty, tx)
 
 
-def prepare_active_tiles(filled, ndvi_g, stats, active, n_active, cap, window, hr, overlap=0, cover_edges=False, clip_ndvi=True):
+def prepare_active_tiles(filled, ndvi_g, stats, active, n_active, cap, window, hr, overlap=0, cover_edges=False, clip_ndvi=True, out=None):
     """-> x (cap,2,hr,hr): x[i] = the network input of tile active[i] for i < min(n_active, cap), the rest untouched; bit-identical
-    to that tile of ``granule_to_tiles(filled, ...)``.  ``active`` / ``n_active``: as ``gaps.select_tiles`` left them."""
+    to that tile of ``granule_to_tiles(filled, ...)``.  ``active`` / ``n_active``: as ``gaps.select_tiles`` left them.  ``out``: a
+    buffer of at least ``cap`` tiles to write into (a captured run's static one); its first ``cap`` tiles are returned."""
     _lib.require_gpu(filled, "filled granule"); _lib.require_gpu(ndvi_g, "ndvi granule")
     _layout(filled, ndvi_g.shape, window, hr, overlap, cover_edges)
     if int(cap) < 1:
         raise _lib.SifsrError(f"cap must be positive, got {cap}")
     h, w = filled.shape
-    x = torch.empty((int(cap), 2, hr, hr), dtype=torch.float32, device=filled.device)
+    x = _tile_buffer(out, int(cap), 2, hr, filled.device, "tile buffer")
     _lib.call("sifsrr_tiles_prepare", filled, ndvi_g, x, active, n_active, int(cap), h, w, window, hr, overlap, 1 if cover_edges else 0,
               *_stats4(stats), 1 if clip_ndvi else 0, _lib.stream_ptr(filled.device))
     return x
@@ -244,3 +251,40 @@ def predict_granule_gaps(model, lst_g, ndvi_g, stats, mask=None, window=64, hr=1
         raise _lib.SifsrError(f"batch must be positive, got {batch}")
     model.eval()
     return _granule.predict_gaps(model, lay, lst_g, ndvi_g, stats, mask, int(batch), fill_value, return_info)
+
+
+class GranulePredictor(_granule.CapturedGranule):
+    """``predict_granule`` -- or, with ``gaps=True``, ``predict_granule_gaps`` -- at ratio ``hr / window`` for ONE granule shape,
+    captured into a hipGraph and replayed per granule (``predict.GranulePredictor`` is the x4 one).  All buffers
+    are static; the tiles are padded to a whole number of batches, so every forward has the captured batch shape.  ``conserve=k``:
+    k ``rconserve.conserve`` steps inside the captured chain (with the mask, when there are gaps).
+
+    ``gaps=False``: ``__call__(lst_g, ndvi_g)`` -> a clone of the raster, the bits of ``predict_granule`` with the same arguments.
+    ``gaps=True``: ``__call__(lst_g, ndvi_g, mask=None, return_info=False)`` -> the bits of ``predict_granule_gaps`` -- at the
+    ``fill_value`` pixels too -- with NO read of the active count: every slot is forwarded and only the active ones are read
+    (``_granule.predict_gaps_fixed``), so granules can follow each other without a host synchronisation, at the price of the
+    forwards of the inactive tiles.  ``info``: "valid" and "n_tiles" as the eager call gives them, "n_active" as a (1,) int32
+    DEVICE tensor.  Everything ``geometry`` refuses is refused here, before any launch; a raster of another shape in the call.
+
+    Which to use (one MI355X, 625 tiles at (64, 192)): give the captured form a ``batch`` that divides the tile count
+    -- at batch 256 it forwards 768 slots, 11.8 ms against 10.3 ms at batch 125.  With 550 of the 625 tiles active the eager
+    ``predict_granule_gaps`` takes 9.3 ms and the best replay 10.3 ms; with 619 active both take 10.3 ms.  The eager call is the one
+    for gappy granules; the captured one for nearly full granules or a host that must not block."""
+
+    def __init__(self, model, lst_shape, stats, window=64, hr=192, overlap=0, cover_edges=False, batch=256, conserve=0, gaps=False,
+                 fill_value=float("nan"), device=None):
+        g = geometry(lst_shape, window, hr, overlap, cover_edges)
+        window, hr, overlap, cover_edges = int(window), int(hr), int(overlap), bool(cover_edges)
+        if gaps and window % 4:
+            raise _lib.SifsrError(f"window must be a multiple of 4 for the tile selection, got {window}")
+        if int(batch) < 1:
+            raise _lib.SifsrError(f"batch must be positive, got {batch}")
+        if not 0 <= int(conserve) <= rconserve.MAX_ITER:
+            raise _lib.SifsrError(f"conserve must be a step count in 0..{rconserve.MAX_ITER}, got {conserve}")
+        dev = device or next(model.parameters()).device
+        self.lst_shape, self.window, self.hr, self.overlap, self.cover_edges = tuple(int(v) for v in lst_shape), window, hr, overlap, cover_edges
+        lay = _layout_record(g, self.lst_shape, window, hr, overlap, cover_edges)
+        self._capture(model, lay, self.lst_shape, stats, batch, conserve, rconserve.conserve, gaps, fill_value, dev)
+
+    def __call__(self, lst_g, ndvi_g, mask=None, return_info=False):
+        return self._replay(lst_g, ndvi_g, mask, return_info)

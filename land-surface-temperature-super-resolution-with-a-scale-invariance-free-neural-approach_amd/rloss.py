@@ -9,20 +9,22 @@ a partly valid patch -- in one call with its gradient.
                                        ``train.eval_step`` / ``train_epoch`` / ``eval_epoch`` / ``fit`` at ``factor``, over the loaders
                                        of patches mined at a ratio (``sifsr.rproducts``)
     adapt_granule                      ``adapt.adapt_granule`` at ratio hr / window: its own checks, then the same loop
+    GraphedTrainStep                   ``train.GraphedTrainStep`` for ``train_step`` at hr / window: the step as one hipGraph, replayed
+                                       (DESIGN.md §9 f23); ``train_epoch`` / ``fit`` / ``adapt_granule`` take it as ``graphed=``
 
 The LR cell of HR pixel (Y, X) is (Y h // H, X w // W): the rule under which ``ratio.predict_granule_gaps`` masks its output.
 Limits (``sifsrq_sif_loss``): 1 < factor <= 8, sides of ceil(factor) + 1 .. 16384, the half width of the sensor model at its
 default ceil(factor), at most 65535 images; ``sensor.sif_loss`` (composed, unmasked) serves what lies beyond them.  Everything is
 fp32 on the device; CPU tensors raise SifsrError: there is no CPU path.
 
-The consistency check and the residual correction at a ratio are ``sifsr.rconserve``.
-Out of scope here: ``GraphedTrainStep`` at a ratio (the call itself can be captured), a captured
-``GranulePredictor`` at a ratio, the ``hkw`` argument in the loss, and bf16."""
+The consistency check and the residual correction at a ratio are ``sifsr.rconserve``; the captured granule
+predictor at a ratio is ``ratio.GranulePredictor`` (§9 f23).
+Out of scope here: gradient exchange inside the captured step, the ``hkw`` argument in the loss, and bf16."""
 from __future__ import annotations
 
 import torch
 
-from . import _lib, adapt, gaps, metrics, ratio, rproducts, sensor, train
+from . import _granule, _lib, adapt, gaps, metrics, ratio, rproducts, sensor, train
 
 MAX_FACTOR = 8.0
 MAX_SIDE = 16384
@@ -218,25 +220,137 @@ def _score(sr, lst_up, valid, masked_metrics, acc, den):
     train._score(sr, lst_up, valid, masked_metrics, acc, den)
 
 
+class GraphedTrainStep:
+    """``train.GraphedTrainStep`` for ``rloss.train_step`` at ``factor = hr / window``: one whole step -- cat,
+    forward, the fused loss at the ratio, backward, Adam -- captured once into a hipGraph and replayed per batch.  The same capture
+    rule (three eager calls, the fourth captures, later calls replay) and the same rules of DESIGN.md §10: the outputs are
+    detached, the optimizer is ``FlatAdam(capturable=True)`` (else ValueError), single GPU (no gradient exchange in the graph).
+
+    Static buffers: ``lst`` (batch,1,window,window), ``lst_up`` and ``ndvi`` (batch,1,hr,hr); ``masked``: also ``valid``
+    (batch,1,window,window) uint8 and ``counts`` (2,) int64.  The captured region forms ``valid_counts(valid, (hr, hr))`` itself
+    and takes the static ``counts`` in its place, by a select on the device, when the call gave counts: one graph serves every
+    mask, with the counts given or formed.  ``return_sr``: the step also returns the static training-mode prediction.
+
+    ``(window, hr)`` must be a pair ``rproducts.trainable`` accepts (SifsrError naming the rule, before any launch).  The step
+    works under ``adapt.frozen_bn(model)``: the mode of the first call is the mode of the warm-up calls, the capture and every replay,
+    and a call whose ``model.bn_frozen`` differs from it is refused."""
+
+    def __init__(self, model, optimizer, batch, stats, alpha, gamma, window, hr, kind="sr2", masked=False, return_sr=False, device=None):
+        rproducts.trainable(window, hr)
+        window, hr = int(window), int(hr)
+        if kind not in _KINDS:
+            raise _lib.SifsrError(f"GraphedTrainStep: kind must be 'sr2' or 'sr1', got {kind!r}")
+        if int(batch) < 1:
+            raise _lib.SifsrError(f"GraphedTrainStep: batch must be positive, got {batch}")
+        if not getattr(optimizer, "capturable", False):
+            raise ValueError("GraphedTrainStep needs FlatAdam(..., capturable=True)")
+        dev = device or next(model.parameters()).device
+        batch = int(batch)
+        self.model, self.opt, self.batch, self.window, self.hr, self.kind = model, optimizer, batch, window, hr, kind
+        self.factor, self.masked, self.return_sr = hr / window, bool(masked), bool(return_sr)
+        self.lst = torch.zeros((batch, 1, window, window), dtype=torch.float32, device=dev)
+        self.lst_up = torch.zeros((batch, 1, hr, hr), dtype=torch.float32, device=dev)
+        self.ndvi = torch.zeros((batch, 1, hr, hr), dtype=torch.float32, device=dev)
+        self.valid = torch.zeros((batch, 1, window, window), dtype=torch.uint8, device=dev) if self.masked else None
+        self.counts = torch.zeros((2,), dtype=torch.int64, device=dev) if self.masked else None
+        self._given = torch.zeros((1,), dtype=torch.bool, device=dev) if self.masked else None
+
+        def step():
+            counts = None
+            if self.masked:
+                counts = torch.where(self._given, self.counts, valid_counts(self.valid, (hr, hr)))
+            out = train_step(model, optimizer, self.lst, self.lst_up, self.ndvi, stats, alpha, gamma, self.factor, kind=kind,
+                             valid=self.valid, counts=counts, sync_grads=False, return_sr=self.return_sr)
+            return tuple(t.detach() for t in out)                       # (detached: train.GraphedTrainStep says why)
+
+        self._eager = step
+        self.graph = None
+        self.bn_frozen = None                                           # the mode of the first call, and of every later one
+        self._warm = 0
+        self.out = None
+
+    def __call__(self, lst, lst_up, ndvi, valid=None, counts=None):
+        """Copies the batch into the static inputs and runs the step; returns the device scalars (ds, pl, loss) and, with
+        ``return_sr``, the prediction -- static tensors once the step replays: the next call overwrites them.  ``masked``:
+        ``valid`` is required, and ``counts`` may be None (formed inside the captured region) or a device (2,) / (b,2) int64
+        tensor (copied / summed on the device, as ``_unpack_batch`` does); otherwise both are refused.  Nothing is read back."""
+        if self.masked != (valid is not None) or (counts is not None and not self.masked):
+            raise ValueError("GraphedTrainStep: valid (and counts) go with masked=True, and valid is required with it")
+        frozen = bool(getattr(self.model, "bn_frozen", False))
+        if self.bn_frozen is None:
+            self.bn_frozen = frozen
+        if frozen != self.bn_frozen:
+            raise ValueError(f"GraphedTrainStep took its first call with model.bn_frozen = {self.bn_frozen}; this call has {frozen}")
+        if counts is not None and (not isinstance(counts, torch.Tensor) or counts.dim() not in (1, 2) or counts.shape[-1:] != (2,)
+                                   or counts.device != self.counts.device):
+            raise ValueError("GraphedTrainStep: counts must be a (2,) or (b,2) integer tensor on the step's device")
+        self.lst.copy_(lst); self.lst_up.copy_(lst_up); self.ndvi.copy_(ndvi)
+        if self.masked:
+            self.valid.copy_(valid.reshape(self.valid.shape))
+            self._given.fill_(counts is not None)
+            if counts is not None:
+                self.counts.copy_(counts.sum(0) if counts.dim() == 2 else counts)
+        if self.graph is not None:
+            self.graph.replay()
+            return self.out
+        if self._warm < 3:
+            self._warm += 1
+            return self._eager()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):          # records the step's kernels; nothing runs yet
+            self.out = self._eager()
+        self.graph = g
+        g.replay()                         # this call's step
+        return self.out
+
+
+def _graphed_for(graphed, model, optimizer, factor, kind, with_metrics, what):
+    """the checks of ``graphed=`` in the epoch loops, before the first batch"""
+    if graphed is None:
+        return
+    if not isinstance(graphed, GraphedTrainStep):
+        raise ValueError(f"{what}: graphed must be an rloss.GraphedTrainStep, got {type(graphed).__name__}")
+    if graphed.model is not model or graphed.opt is not optimizer or graphed.kind != kind or graphed.factor != float(factor):
+        raise ValueError(f"{what}: the captured step was built for another model, optimizer, kind or factor "
+                         f"(kind {graphed.kind!r}, factor {graphed.factor:g}; the call: {kind!r}, {float(factor):g})")
+    if with_metrics and not graphed.return_sr:
+        raise ValueError(f"{what}: with_metrics needs a GraphedTrainStep built with return_sr=True")
+
+
+def _train_epoch(model, loader, optimizer, stats, alpha, gamma, factor, kind, device, with_metrics, masked_metrics, graphed=None):
+    _graphed_for(graphed, model, optimizer, factor, kind, with_metrics, "train_epoch")
+    acc = torch.zeros(5, dtype=torch.float64, device=device)
+    den = torch.zeros(5, dtype=torch.float64, device=device)
+    n = 0
+    for batch in loader:
+        lst, lst_up, ndvi, valid, counts = _unpack_batch(batch, device)
+        if graphed is not None and lst.shape[0] == graphed.batch:
+            ds, pl, loss, *sr = graphed(lst, lst_up, ndvi, valid, counts)
+            sr = sr[0] if sr else None
+        else:                                                            # (no step given, or a shorter last batch: batch statistics forbid padding)
+            ds, pl, loss, sr = train_step(model, optimizer, lst, lst_up, ndvi, stats, alpha, gamma, factor, kind, valid=valid, counts=counts,
+                                          return_sr=True)
+        acc[0] += ds.detach(); acc[1] += pl.detach(); acc[2] += loss.detach()
+        if with_metrics:
+            _score(sr, lst_up, valid, masked_metrics, acc, den)
+        n += 1
+    return train._epoch_means(acc, den, n, with_metrics)
+
+
+@_granule.keyword_options(_train_epoch, graphed=None)
 def train_epoch(model, loader, optimizer, stats, alpha, gamma, factor, kind="sr2", device="cuda", with_metrics=True,
                 masked_metrics=False):
     """``train.train_epoch`` at ``factor``: one ``rloss.train_step`` per batch of ``loader`` (``MinedPatches.loader`` /
     ``masked_loader`` of patches mined by ``rproducts.PatchMiner``; batches of three, or of five with the counts), -> the epoch means
     (ds_loss, percep_loss, loss, psnr, ssim), read back ONCE per epoch.  PSNR / SSIM score the training-mode prediction against
     ``lst_up``; ``masked_metrics``: over the HR pixels under valid cells only (``rproducts.expand_valid``, then
-    ``metrics.masked_psnr_ssim``)."""
-    acc = torch.zeros(5, dtype=torch.float64, device=device)
-    den = torch.zeros(5, dtype=torch.float64, device=device)
-    n = 0
-    for batch in loader:
-        lst, lst_up, ndvi, valid, counts = _unpack_batch(batch, device)
-        ds, pl, loss, sr = train_step(model, optimizer, lst, lst_up, ndvi, stats, alpha, gamma, factor, kind, valid=valid, counts=counts,
-                                      return_sr=True)
-        acc[0] += ds.detach(); acc[1] += pl.detach(); acc[2] += loss.detach()
-        if with_metrics:
-            _score(sr, lst_up, valid, masked_metrics, acc, den)
-        n += 1
-    return train._epoch_means(acc, den, n, with_metrics)
+    ``metrics.masked_psnr_ssim``).
+
+    Keyword-only ``graphed=step`` (``_granule.keyword_options``; default None: the calls above, bit for bit): an
+    ``rloss.GraphedTrainStep`` built for this model, optimizer, kind and factor -- with ``return_sr=True`` when ``with_metrics`` --
+    takes the batches of its captured size; a shorter last batch runs the eager ``train_step`` (batch statistics forbid
+    padding)."""
 
 
 @torch.inference_mode()
@@ -257,27 +371,28 @@ def eval_epoch(model, loader, stats, alpha, gamma, factor, kind="sr2", device="c
     return train._epoch_means(acc, den, n, with_metrics)
 
 
+def _fit(model, train_loader, val_loader, n_epochs, optimizer, stats, alpha, gamma, factor, kind, checkpoint, masked_metrics, graphed=None):
+    _graphed_for(graphed, model, optimizer, factor, kind, True, "fit")
+    device = next(model.parameters()).device
+    return train._fit(model, n_epochs, checkpoint,
+                      lambda: train_epoch(model, train_loader, optimizer, stats, alpha, gamma, factor, kind, device, masked_metrics=masked_metrics,
+                                          graphed=graphed),
+                      lambda: eval_epoch(model, val_loader, stats, alpha, gamma, factor, kind, device, masked_metrics=masked_metrics))
+
+
+@_granule.keyword_options(_fit, graphed=None)
 def fit(model, train_loader, val_loader, n_epochs, optimizer, stats, alpha, gamma, factor, kind="sr2", checkpoint=None,
         masked_metrics=False):
     """``train.fit`` at ``factor`` over two loaders (``MinedPatches.loader`` / ``masked_loader``, which shuffle per epoch themselves):
     per epoch one ``train_epoch`` and one ``eval_epoch``, the same ``metrics`` dict, ``best_epoch`` rule and restore of the best
-    state through ``checkpoint`` (``train.ModelCheckpoint``).  Returns (model, metrics)."""
-    device = next(model.parameters()).device
-    return train._fit(model, n_epochs, checkpoint,
-                      lambda: train_epoch(model, train_loader, optimizer, stats, alpha, gamma, factor, kind, device, masked_metrics=masked_metrics),
-                      lambda: eval_epoch(model, val_loader, stats, alpha, gamma, factor, kind, device, masked_metrics=masked_metrics))
+    state through ``checkpoint`` (``train.ModelCheckpoint``).  Returns (model, metrics).
+
+    Keyword-only ``graphed=step``: as in ``train_epoch`` (an ``rloss.GraphedTrainStep`` with ``return_sr=True``; the validation
+    pass and a restore of the best state run as they did: the parameters keep their addresses)."""
 
 
-def adapt_granule(model, lst_g, ndvi_g, stats, window, hr, mask=None, steps=20, lr=1e-5, alpha=0.5, gamma=1.0, kind="sr2", batch=16,
-                  overlap=0, cover_edges=False, optimizer=None):
-    """``adapt.adapt_granule`` at ratio ``hr / window``: ``steps`` optimisation steps of the masked loss on the active tiles of one
-    gappy granule (raw LST (h,w) [K], raw NDVI (h p/q, w p/q), ``mask`` as in ``gaps.fill_gaps``), BatchNorm statistics frozen.
-    The layout is ``ratio.geometry``'s; fill, selection and loss targets are ``gaps.fill_gaps``, ``gaps.select_tiles`` and
-    ``adapt.tile_targets`` (they see the LST raster only), the network inputs ``ratio.prepare_active_tiles``; step i is
-    ``rloss.train_step(..., factor=hr / window, valid=)`` on the min(batch, n_active) tiles from position i * batch of the active
-    list, cyclic.  A ``(window, hr)`` whose ``sensor.lr_shape(hr, hr, hr / window)`` is not ``(window, window)`` -- (16, 20): the
-    sensor model's crop leaves 17 -- is refused before any launch.  The read of the active count is the only host synchronisation;
-    no active tile: no step, no forward.  Returns an ``adapt.Adaptation``; the model's mode and ``bn_frozen`` are as they were."""
+def _adapt_granule(model, lst_g, ndvi_g, stats, window, hr, mask, steps, lr, alpha, gamma, kind, batch, overlap, cover_edges, optimizer,
+                   graphed=False):
     for t, n in ((lst_g, "lst granule"), (ndvi_g, "ndvi granule")):
         if not isinstance(t, torch.Tensor):
             raise _lib.SifsrError(f"adapt_granule: {n} must be a tensor, got {type(t).__name__}")
@@ -307,4 +422,26 @@ def adapt_granule(model, lst_g, ndvi_g, stats, window, hr, mask=None, steps=20, 
     def step(model, optimizer, lst, xb, vt, n_valid):                       # (the fused loss forms its own counts from vt)
         return train_step(model, optimizer, lst, xb[:, 0:1], xb[:, 1:2], stats, alpha, gamma, factor, kind=kind, valid=vt)
 
-    return adapt._adapt(model, lay, step, lst_g, ndvi_g, stats, mask, int(steps), int(batch), lr, optimizer)
+    def captured(model, optimizer, b):
+        g = GraphedTrainStep(model, optimizer, b, stats, alpha, gamma, window, hr, kind=kind, masked=True)
+        return lambda model, optimizer, lst, xb, vt, n_valid: g(lst, xb[:, 0:1], xb[:, 1:2], vt)
+
+    return adapt._adapt(model, lay, step, lst_g, ndvi_g, stats, mask, int(steps), int(batch), lr, optimizer, captured if graphed else None)
+
+
+@_granule.keyword_options(_adapt_granule, graphed=False)
+def adapt_granule(model, lst_g, ndvi_g, stats, window, hr, mask=None, steps=20, lr=1e-5, alpha=0.5, gamma=1.0, kind="sr2", batch=16,
+                  overlap=0, cover_edges=False, optimizer=None):
+    """``adapt.adapt_granule`` at ratio ``hr / window``: ``steps`` optimisation steps of the masked loss on the active tiles of one
+    gappy granule (raw LST (h,w) [K], raw NDVI (h p/q, w p/q), ``mask`` as in ``gaps.fill_gaps``), BatchNorm statistics frozen.
+    The layout is ``ratio.geometry``'s; fill, selection and loss targets are ``gaps.fill_gaps``, ``gaps.select_tiles`` and
+    ``adapt.tile_targets`` (they see the LST raster only), the network inputs ``ratio.prepare_active_tiles``; step i is
+    ``rloss.train_step(..., factor=hr / window, valid=)`` on the min(batch, n_active) tiles from position i * batch of the active
+    list, cyclic.  A ``(window, hr)`` whose ``sensor.lr_shape(hr, hr, hr / window)`` is not ``(window, window)`` -- (16, 20): the
+    sensor model's crop leaves 17 -- is refused before any launch.  The read of the active count is the only host synchronisation;
+    no active tile: no step, no forward.  Returns an ``adapt.Adaptation``; the model's mode and ``bn_frozen`` are as they were.
+
+    Keyword-only ``graphed=True`` (``_granule.keyword_options``; default False: the loop above, bit for bit): after the read of the
+    active count the step is an ``rloss.GraphedTrainStep(masked=True)`` for min(batch, n_active) tiles -- three eager steps, the
+    fourth captures, the rest replay; with no optimizer given the loop makes ``FlatAdam(lr=lr, capturable=True)``, and one that is
+    given must be capturable (ValueError before any launch)."""
