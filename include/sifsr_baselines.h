@@ -15,6 +15,7 @@
  * operator, like sifsr_fft2_attenuation): one rounding, at the final float32 store.  No atomics: every reduction runs in a fixed
  * order (wavefront shuffles, then LDS), so results are deterministic and the rows of a batch do not depend on each other.
  * Every output is written in full.
+ * Any other ratio H / h <= 8 (kriging: integer scales 2..8): sifsr/rbaselines.py, csrc/rbaselines_api.h.
  */
 #ifndef SIFSR_BASELINES_H
 #define SIFSR_BASELINES_H

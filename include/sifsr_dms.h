@@ -16,6 +16,7 @@
  * Shapes: lst is (B, h, w) float32 in Kelvin (coarse), ndvi_f, sr and out are (B, 4h, 4w) float32 (fine); N = h * w.  Only scale 4
  * is built.  Intermediate results are float64 with one rounding at a float32 store.  No atomics: every reduction runs in a fixed
  * order, so results are deterministic and the images of a batch do not depend on each other.  Every output is written in full.
+ * Any other ratio H / h <= 8: sifsr/rbaselines.py, csrc/rbaselines_api.h.
  */
 #ifndef SIFSR_DMS_H
 #define SIFSR_DMS_H

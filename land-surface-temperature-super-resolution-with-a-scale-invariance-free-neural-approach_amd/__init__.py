@@ -54,6 +54,10 @@ Drop-in surface (SURVEY.md §8 b):
                                        predictors as one hipGraph each; the gap-aware predictor forwards a fixed number of slots and
                                        keeps the active count on the device, so a stream of granules has no host synchronisation
                                        (host code only: no kernel, no header)
+  rbaselines.tsharp / atprk / aatprk / dms / dms_model / dms_apply / dms_aggregate  <- utils.py:876-1606 with `iscale` other than 4
+                                       (DESIGN.md §9 f24): the comparison methods for a fine raster at any ratio H / h <= 8 (kriging at
+                                       integer scales 2..8), so that a model trained at x3, x2.5 or x2 can be ranked against them
+                                       (csrc/rbaselines_api.h)
   products.decode / PatchMiner / MinedPatches, dataset.MinedDataset  <- process_modis.py:38-335, data_preparation.py:32-102
                                        (raw granule arrays -> patches + statistics.json, on device)
 
@@ -64,7 +68,7 @@ and registers ``sifsr`` / ``sifsr.<submodule>`` as aliases of the same module ob
 import importlib
 import sys
 
-_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "degrade", "predict", "baselines", "products", "lpips", "adapt", "sensor", "rconserve", "ratio", "rloss", "rproducts")
+_SUBMODULES = ("_lib", "model", "sif_ops", "optim", "dataset", "distributed", "train", "pipeline", "metrics", "fourier", "spectra", "gaps", "conserve", "degrade", "predict", "baselines", "products", "lpips", "adapt", "sensor", "rconserve", "ratio", "rloss", "rproducts", "rbaselines")
 for _m in _SUBMODULES:
     importlib.import_module(__name__ + "." + _m)
 

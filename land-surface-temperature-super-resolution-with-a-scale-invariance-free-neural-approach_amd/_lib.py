@@ -142,6 +142,17 @@ def lib():
     return _lib
 
 
+def bind_header(path: str):
+    """Bind the SIFSR_API declarations of a header that is NOT a row of FAMILIES (one inside the package, whose module gates it
+    itself) on the handle of lib(), with the declared types.  -> {name: (restype, [Arg])}.  call() then serves them like any other."""
+    handle, decls = lib(), parse_header(path)
+    for name, (ret, args) in decls.items():
+        fn = getattr(handle, name)         # AttributeError if the library lacks a declared symbol
+        fn.restype = ret
+        fn.argtypes = [t for _, t in args]
+    return decls
+
+
 def _conv(v):
     if v is None:
         return None

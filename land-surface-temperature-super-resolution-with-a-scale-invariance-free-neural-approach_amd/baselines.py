@@ -33,6 +33,7 @@ import torch
 
 from . import _lib
 
+# At any other ratio H / h <= 8 (kriging: integer scales 2..8) the same seven functions are sifsr.rbaselines.
 KS = (0, 1, 2, 4, 5, 8, 9, 10, 13, 16, 17, 18, 20, 25, 32)       # squared coarse distances inside a 5 x 5 block
 LM_MAX_ITER = 200
 
@@ -290,8 +291,13 @@ def dms_training_set(lst, ndvi_fine):
     """Stages 1 and 2 -> dict(x, cv, weight (B,N) float64, good (B,N) bool, threshold (B,) float64, n_train (B,) int32: 0 where
     fewer than 10 cells are good).  The percentile's sort is torch.sort."""
     B, h, w = _check_dms(lst, ndvi_fine)
-    N, s, dev = h * w, _lib.stream_ptr(lst.device), lst.device
     mean, std = dms_aggregate(ndvi_fine)
+    return _training_set(lst, mean, std, B, h, w)
+
+
+def _training_set(lst, mean, std, B, h, w):
+    """stage 2 on the cell statistics (B,h,w) of stage 1: nothing here knows the ratio (sifsr.rbaselines calls it too)"""
+    N, s, dev = h * w, _lib.stream_ptr(lst.device), lst.device
     x, cv = _f64((B, N), lst), _f64((B, N), lst)
     good = torch.empty((B, N), dtype=torch.uint8, device=dev)
     _lib.call("sifsrd_trainset", lst, mean, std, x, cv, good, B, h, w, s)
@@ -335,10 +341,20 @@ def dms_model(lst, ndvi_fine, *, n_estimators=10, counts=None, seed=0):
     """Stages 1-3: fit the bagged trees of every image.  -> dict(thresholds (B,E,29) float64 ascending, +inf padded; nleaf (B,E)
     int32; leaves (B,E,30,4) float64 = coef, intercept, lo, hi; n_train (B,) int32; counts (B,E,h*w) int32)."""
     B, h, w = _check_dms(lst, ndvi_fine)
-    E, N, s, dev = int(n_estimators), h * w, _lib.stream_ptr(lst.device), lst.device
+    E = _estimators(n_estimators)
+    return _fit_model(lst, dms_training_set(lst, ndvi_fine), B, h, w, E, counts, seed)
+
+
+def _estimators(n_estimators):
+    E = int(n_estimators)
     if not 1 <= E <= 32:
         raise ValueError(f"n_estimators must be in [1, 32], got {n_estimators}")
-    ts = dms_training_set(lst, ndvi_fine)
+    return E
+
+
+def _fit_model(lst, ts, B, h, w, E, counts, seed):
+    """stage 3 on a training set of coarse cells: nothing here knows the ratio (sifsr.rbaselines calls it too)"""
+    N, s, dev = h * w, _lib.stream_ptr(lst.device), lst.device
     good, n_train = ts["good"], ts["n_train"]
     if counts is None:
         counts = _bootstrap_counts(good, n_train, E, seed)

@@ -20,6 +20,8 @@
 
 #pragma clang fp contract(off)
 
+#include "dms_dev.h"      // pow4d, tree_value: shared with rbaselines.hip
+
 namespace {
 
 constexpr int MAXL = SIFSRD_MAX_LEAVES;      // 30
@@ -29,7 +31,6 @@ constexpr int MINLEAF = 10;
 constexpr int NT = 256;
 
 __device__ __forceinline__ double dinf() { return __longlong_as_double(0x7FF0000000000000ll); }
-__device__ __forceinline__ double pow4d(double v) { return (v * v) * (v * v); }
 
 __global__ __launch_bounds__(256) void dms_aggregate_kernel(const float* __restrict__ fine, double* __restrict__ mean,
                                                             double* __restrict__ sd, int h, int w, size_t cells, int pow4) {
@@ -344,16 +345,6 @@ __global__ __launch_bounds__(NT) void dms_fit_kernel(const double* __restrict__ 
 
 // ---- stage 4 ----------------------------------------------------------------------------------------------------------------
 constexpr int ROWS = 4;      // coarse rows per workgroup
-
-__device__ __forceinline__ double tree_value(const double* thr, const double* lf, int L, double x) {
-  int a = 0, z = L - 1;
-  while (a < z) {
-    const int mid = (a + z) >> 1;
-    if (thr[mid] < x) a = mid + 1; else z = mid;
-  }
-  const double* p = lf + 4 * a;
-  return fmin(fmax(x * p[0] + p[1], p[2]), p[3]);
-}
 
 __global__ __launch_bounds__(256) void dms_predict_kernel(const float* __restrict__ ndvi, const double* __restrict__ thresholds,
                                                           const int* __restrict__ nleaf, const double* __restrict__ leaves,
